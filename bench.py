@@ -27,8 +27,13 @@ grows (weak scaling).  Model: the reference actor-critic (model.py), random init
 Precision: the headline runs at the reference's precision, fp32 (model.py / train.py are fp32
 end to end): ``--dtype bf16x3`` = every GEMM on split-bf16 operands (x = hi + lo, three bf16
 MFMAs per product, fp32 accumulate; fp32 tolerances in tests/test_gpu_kernels.py), fp32 master
-weights, fp32 loss/GAE/Adam.  The reduced-precision modes (bf16, fp8 forward) are timed in the
-same invocation on the same config and reported as separately labelled ``variants``.
+weights, fp32 loss/GAE/Adam.  A plain run times the headline precision only.  ``--full`` also
+times the reduced-precision modes (``--variants``: bf16, fp8 forward) in the same invocation on
+the same config and reports them as separately labelled ``variants``.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed iteration left
+its caller as ``DIR/<name>.npy`` (dump_outputs below); the seed is fixed, so two builds run
+with the same arguments see identical inputs and can be compared output for output.
 
 Timing: W untimed warmup iterations; barrier + device sync; K timed iterations; barrier +
 device sync; the max over ranks of the elapsed time.  Rank 0 prints ONE JSON line.  The
@@ -45,6 +50,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -97,6 +103,25 @@ def check_world(gpus: int, backend: str) -> None:
                          f"process per GPU)")
 
 
+DUMP_METRICS = ("loss", "loss_clip", "loss_value", "loss_ent", "grad_norm", "mean_ep_return", "ep_count")
+
+
+def dump_outputs(out_dir: str, w, m: dict) -> None:
+    """What the headline run's last timed iteration left its caller, as ``<name>.npy``:
+    ``params`` (the flat fp32 master parameters after the last Adam step), ``obs_mean`` /
+    ``obs_inv_std`` (the running observation normalisation the next rollout reads), fp32; and
+    ``metrics`` (float64, the DUMP_METRICS of the last iteration in that order, nan = absent).
+    A few hundred kB in all at the reference model."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"params": w.model.flat.data.detach().float().cpu().numpy(),
+              "obs_mean": w.stats.mean_f32.detach().float().cpu().numpy(),
+              "obs_inv_std": w.stats.inv_std_f32.detach().float().cpu().numpy(),
+              "metrics": np.array([float(m.get(k, float("nan"))) for k in DUMP_METRICS], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -109,9 +134,13 @@ def main():
     ap.add_argument("--dtype", default="bf16x3",
                     help="headline operand precision: bf16x3 (fp32-accurate, default), fp32 (exact f32 MFMA), "
                          "bf16, fp8")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the --variants dtypes after the headline (a plain run times the headline only)")
     ap.add_argument("--variants", default="bf16,fp8",
-                    help="comma list of extra dtypes timed after the headline on the same config "
+                    help="with --full: comma list of extra dtypes timed after the headline on the same config "
                          "(reported under 'variants'; '' = none)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the headline run's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--batch-size", type=int, default=0, help="0 = full buffer (reference DPPO)")
     ap.add_argument("--overlap-rollout", nargs="?", const="on", default="auto", choices=["auto", "on", "off"],
                     help="the last value-head all-reduce + Adam overlap the next rollout on a side stream (exact: "
@@ -226,9 +255,13 @@ def main():
     n_iter = args.warmup + args.steps
     side_steps, pend_steps = int(getattr(w.engine, "side_steps", 0)), int(getattr(w.engine, "pending_steps", 0))
     overlap_value_step = "side_stream" if side_steps else ("pending_work" if pend_steps else "none")
+    if args.dump_outputs:
+        w.quiesce()              # every rank: a value-head step still on the side stream is applied first
+        if ctx.rank == 0:
+            dump_outputs(args.dump_outputs, w, m)
     del w
     variants = {}
-    for dt in [d for d in args.variants.split(",") if d and d != args.dtype]:
+    for dt in ([d for d in args.variants.split(",") if d and d != args.dtype] if args.full else []):
         el_v, _, wv, _ = run(dt)
         variants[dt] = {"value": total_steps / el_v, "ms_per_step": el_v / args.steps * 1e3,
                         "dtype": DTYPE_LABEL[dt], "vs_headline": (total_steps / el_v) / value}

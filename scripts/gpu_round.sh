@@ -8,7 +8,7 @@
 # the first failing one — a failed step may be a GPU fault, so nothing else runs on the GPU after):
 #   tests      pytest -m gpu (TESTS_K: a -k filter)
 #   smoke      __graft_entry__.smoke()
-#   bench      bench.py --steps $BSTEPS --warmup 3 (BENCH_ARGS: extra flags)
+#   bench      bench.py --full --steps $BSTEPS --warmup 3: headline + variants (BENCH_ARGS: extra flags)
 #   ab         bench.py arms alternated $AB_REPS times: AB_ARMS="name=flags;name=flags"
 #   stats      rocprofv3 --kernel-trace --stats of bench.py per dtype in $DTYPES -> $OUT/s_<dtype>
 #   pmc        PMC passes of the hot kernels (scripts/pmc.sh; REGEX, BENCH_ARGS)
@@ -35,7 +35,7 @@ for s in ${STEPS:-tests smoke bench}; do
     tests) run pytest_gpu 1500 python -u -m pytest tests -v -m gpu -x -p no:cacheprovider --timeout 240 \
              --timeout-method thread ${TESTS_K:+-k "$TESTS_K"} || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 600 python bench.py --steps "$BSTEPS" --warmup 3 ${BENCH_ARGS:-} || exit $? ;;
+    bench) run bench 600 python bench.py --full --steps "$BSTEPS" --warmup 3 ${BENCH_ARGS:-} || exit $? ;;
     ab)    IFS=';' read -ra ARMS <<< "${AB_ARMS:?AB_ARMS=name=flags;...}"
            for i in $(seq 1 "${AB_REPS:-2}"); do
              for arm in "${ARMS[@]}"; do

@@ -41,8 +41,8 @@ def _check(d: dict, n: int, variants: list) -> None:
 def test_bench_json_line_one_gpu():
     from pytorch_dppo_amd.runtime.launcher import free_port
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))   # its world-1 RCCL group
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *TINY, "--variants", "bf16"], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *TINY, "--full", "--variants", "bf16"], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     _check(_json_line(r.stdout), 1, ["bf16"])
 
@@ -83,6 +83,30 @@ def test_bench_one_gpu_reports_rccl_world():
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 1 and d["config"]["rccl_world_size"] == 1 and d["config"]["dist_backend"] == "nccl"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_headline_only_and_dumps_outputs(tmp_path):
+    """without --full the variants are not run (whatever --variants defaults to), and
+    --dump-outputs leaves the last timed iteration's outputs as finite fp32/fp64 .npy arrays"""
+    import numpy as np
+    from pytorch_dppo_amd.runtime.launcher import free_port
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *TINY, "--dump-outputs", str(out)], cwd=ROOT,
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    _check(d, 1, [])
+    assert d["ms_per_step"] > 0
+    assert sorted(p.name for p in out.iterdir()) == ["metrics.npy", "obs_inv_std.npy", "obs_mean.npy", "params.npy"]
+    arrays = {p.stem: np.load(p) for p in out.iterdir()}
+    assert arrays["params"].dtype == np.float32 and arrays["params"].ndim == 1 and arrays["params"].size > 376 * 500
+    assert arrays["obs_mean"].shape == arrays["obs_inv_std"].shape == (376,)
+    assert arrays["metrics"].dtype == np.float64 and arrays["metrics"][0] == pytest.approx(d["config"]["last_iter"]["loss"])
+    assert all(np.isfinite(a).all() for n, a in arrays.items() if n != "metrics")
+    assert np.abs(arrays["obs_mean"]).max() > 0          # the rollouts' statistics, not the initial zeros
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
 
 
 def _bench_fails(args, extra_env):

@@ -919,7 +919,7 @@ def test_two_ranks_on_one_gpu_stay_in_sync(extra):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--num-envs", "2048", "--verify-sync", "--variants", "bf16,fp8",
+           "--steps", "2", "--warmup", "1", "--num-envs", "2048", "--verify-sync", "--full", "--variants", "bf16,fp8",
            "--dist-backend", "gloo"] + extra
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
