@@ -230,6 +230,52 @@ void rollout_stepnorm(int64_t dt, int64_t rows, torch::Tensor state, torch::Tens
   after_launch(__func__);
 }
 
+// Batched policy evaluation (csrc/eval.hip): E fresh envs run to the end of their first episode;
+// writes ret [E] fp32 / len [E] int32 and nothing else.  ints: kind,E,O,A,S,limit,std_var,
+// deterministic; keys: env,term,reset,action.
+void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales,
+                  torch::Tensor flat, torch::Tensor mean, torch::Tensor inv_std, torch::Tensor ret, torch::Tensor len,
+                  std::vector<int64_t> ints, std::vector<int64_t> keys, torch::Tensor qscale) {
+  TORCH_CHECK(dt >= 0 && dt <= 3, "dt");
+  TORCH_CHECK(ints.size() == 8, "ints: kind,E,O,A,S,limit,std_var,deterministic");
+  TORCH_CHECK(keys.size() == 4, "keys: env,term,reset,action");
+  TORCH_CHECK(scales.size() >= 3, "scales");
+  Layout L = parse_layout(layout);
+  EvalArgs a{};
+  TORCH_CHECK(ints[1] > 0 && ints[1] <= (int64_t)1 << 30, "E must be in [1, 2^30], got ", ints[1]);
+  TORCH_CHECK(ints[5] >= 1 && ints[5] <= (int64_t)1 << 20, "limit must be in [1, 2^20], got ", ints[5]);
+  a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
+  a.limit = (int)ints[5]; a.std_var = ints[6] ? 1 : 0; a.deterministic = ints[7] ? 1 : 0;
+  TORCH_CHECK(a.kind == 0 || a.kind == 1, "kind");
+  TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
+  TORCH_CHECK(a.kind == 0 ? a.S == a.O : (a.S == 2 && a.O == 3), "state dims");
+  TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
+  TORCH_CHECK(L.d_in[1] > L.n_out[0] && L.d_in[2] > L.n_out[1], "layout: hidden widths");
+  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
+  check(flat, "flat", at::kFloat, a.A);
+  check(mean, "mean", at::kFloat, a.O);
+  check(inv_std, "inv_std", at::kFloat, a.O);
+  check(ret, "ret", at::kFloat, a.E);
+  check(len, "len", at::kInt, a.E);
+  TORCH_CHECK(ret.numel() == a.E && len.numel() == a.E, "ret / len must have exactly E = ", a.E, " elements, got ",
+              ret.numel(), " / ", len.numel());
+  a.key_env = (uint32_t)keys[0]; a.key_term = (uint32_t)keys[1]; a.key_reset = (uint32_t)keys[2];
+  a.key_action = (uint32_t)keys[3];
+  a.W = wimg.data_ptr();
+  a.off_w1 = L.off_w[0]; a.off_w2 = L.off_w[1]; a.off_w3 = L.off_w[2];
+  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
+  a.n1 = L.n_out[0]; a.n2 = L.n_out[1]; a.n3 = L.n_out[2];
+  a.qscale = opt_scales(qscale);
+  a.s1 = (float)scales.at(0); a.s2 = (float)scales.at(1); a.s3 = (float)scales.at(2);
+  a.log_std = flat.data_ptr<float>();
+  a.mean = mean.data_ptr<float>();
+  a.inv_std = inv_std.data_ptr<float>();
+  a.ret = ret.data_ptr<float>();
+  a.len = len.data_ptr<int>();
+  launch_eval((int)dt, a, cur_stream());
+  after_launch(__func__);
+}
+
 // the largest env-tile grid the per-step normalisation launch can run co-resident
 int64_t rollout_stepnorm_cap_b(int64_t dt, int64_t rows, std::vector<int64_t> layout, int64_t O, int64_t A, int64_t S) {
   Layout L = parse_layout(layout);
@@ -835,6 +881,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_comm(m);
   m.def("rollout", &rollout);
   m.def("rollout_stepnorm", &rollout_stepnorm);
+  m.def("eval_rollout", &eval_rollout);
   m.def("rollout_stepnorm_cap", &rollout_stepnorm_cap_b);
   m.def("mlp_value", &mlp_value);
   m.def("mlp_train", &mlp_train);

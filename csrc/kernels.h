@@ -74,6 +74,31 @@ inline __host__ __device__ size_t sn_g1_elems(int nblk, int O) {
   return (size_t)2 * ((O + 3) >> 2) * ((nblk + 3) >> 2) * 16;
 }
 
+// Batched policy evaluation (csrc/eval.hip): E fresh envs, each from its reset to the end of its
+// first episode.  The env state lives in LDS only; the launch writes ret / len and nothing else.
+struct EvalArgs {
+  int kind;            // 0 synthetic, 1 pendulum
+  int E, O, A, S;      // envs, obs dims, act dims, state dims
+  int limit;           // episode step limit (the launch's loop bound)
+  int deterministic;   // 1: a = mu, 0: a = mu + sigma * eps (eps keyed: action key, env, step)
+  uint32_t key_env, key_term, key_reset, key_action;
+  // policy (packed weight image, storage precision): RolloutArgs' fields
+  const void* W;
+  int off_w1, off_w2, off_w3;
+  int d1, d2, d3;
+  int n1, n2, n3;
+  float s1, s2, s3;
+  const float* qscale;
+  const float* log_std;  // [A] fp32 master
+  int std_var;
+  // fixed observation normalisation
+  const float* mean;     // [O]
+  const float* inv_std;  // [O]
+  // outputs, frozen at an env's first done
+  float* ret;          // [E] sum of the unclipped rewards, added in step order
+  int* len;            // [E] steps
+};
+
 // fp8 mode's gradient-amax ring (csrc/common.h Q8): [3 slots][4 tensors][Q8_SUB sub-slots][Q8_LINE]
 constexpr int Q8_SUB = 64, Q8_LINE = 32;
 constexpr int Q8_SLOT = 4 * Q8_SUB * Q8_LINE;   // dwords per ring slot
@@ -217,6 +242,7 @@ void launch_debug_invalid(double* out, hipStream_t s);   // test hook: a launch 
 void launch_rollout(int dt, const RolloutArgs& a, int rows, hipStream_t s);
 void set_rollout_waves(int nw);                 // 4 or 8 waves per rollout workgroup (A/B)
 int rollout_stepnorm_cap(int dt, const RolloutArgs& a, int rows);   // co-resident grid of the SN launch
+void launch_eval(int dt, const EvalArgs& a, hipStream_t s);   // 16 envs per workgroup (csrc/eval.hip)
 void launch_mlp_value(int dt, const MlpArgs& a, hipStream_t s);
 void launch_mlp_train(int dt, const MlpArgs& a, hipStream_t s);
 size_t mlp_train_lds_bytes(int dt, const MlpArgs& a);

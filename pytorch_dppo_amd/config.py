@@ -64,6 +64,10 @@ class Params:
     eval_every: int = 0                  # evaluator snapshot period in iterations (0 = off)
     eval_episodes: int = 1
     eval_sleep: float = 0.0              # test.py:63 sleeps 10 s per episode; default no sleep
+    eval_mode: str = "process"           # process (the CPU evaluator process, one env) | inline (batched, in the
+                                         # trainer's engine: csrc/eval.hip on the GPU engine, its torch twin on the CPU one)
+    eval_envs: int = 256                 # inline: evaluation envs (one first episode each)
+    eval_deterministic: bool = False     # inline: act with mu (the reference acts stochastically, test.py:40-44)
     checkpoint_dir: str = ""
     checkpoint_every: int = 0
     resume: str = ""
@@ -148,6 +152,12 @@ class Params:
             self.std_convention = "var"
         if self.obs_norm_update not in ("step", "rollout"):
             raise ValueError("obs_norm_update must be step|rollout")
+        if self.eval_mode not in ("process", "inline"):
+            raise ValueError(f"eval_mode must be process|inline, got {self.eval_mode}")
+        if int(self.eval_envs) < 1:
+            raise ValueError(f"eval_envs must be >= 1, got {self.eval_envs}")
+        if self.eval_mode == "inline" and self.env_backend == "gym":
+            raise ValueError("eval_mode=inline evaluates the builtin envs; env_backend=gym needs eval_mode=process")
         for name, ok in (("dist_backend", ("auto", "nccl", "gloo")), ("grad_comm", ("auto", "native", "process_group")),
                          ("update_kernels", ("auto", "heads", "tile")), ("stats_stream", ("off", "on", "auto"))):
             if getattr(self, name) not in ok:

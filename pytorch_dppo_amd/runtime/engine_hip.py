@@ -158,6 +158,7 @@ class HipEngine:
         self._sn_bufs = None       # its granule buffers, timeout word (+ pinned copy)
         self._sn_epoch = 1         # its next granule tag (never reused)
         self._obs_scratch = None   # obs_observe partials + fp64 sums
+        self._eval_bufs: Dict[int, tuple] = {}   # evaluate(): (ret, len) outputs per env count
         # ---- update geometry ----
         self.mb = params.minibatch_rows()
         # per-head streaming kernels (csrc/mlp_head.hip, 128 rows per workgroup): split-bf16 and
@@ -848,6 +849,42 @@ class HipEngine:
         # everything stays on the device: no host sync inside the iteration
         return {"count": float(self.N), "s1": s1, "s2": s2, "shift": shift,
                 "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
+
+    @torch.no_grad()
+    def evaluate(self, num_envs: int, deterministic: bool = False):
+        """Batched evaluation of the current policy (csrc/eval.hip): ``num_envs`` fresh evaluation
+        envs (runtime/evaluator.py eval_keys: env seed + 7777, rank 0, the evaluator's action
+        stream), each from its reset to the end of its first episode, under the current fp32
+        images of ``self.stats``.  ONE launch on the current stream, no host sync; returns the
+        device tensors ``(ret fp32 [E], len int32 [E])`` this engine owns (rewritten by the next
+        call for the same ``num_envs``).  Reads the policy image, log_std and the stats; writes
+        nothing but its own outputs (no env state, buffers, stats, parameters or optimizer state)."""
+        from .evaluator import eval_keys
+        if self.host_env:
+            raise RuntimeError("evaluate() runs the builtin envs in-kernel; a host-stepped (gym) env has no "
+                               "device evaluation (use eval_mode='process')")
+        E = int(num_envs)
+        if E <= 0:
+            raise ValueError(f"num_envs must be positive, got {num_envs}")
+        # as rollout(): fp8's forward image follows the weights only through the refresh, which
+        # reads every layer — a value step still pending / on the side stream is joined first
+        if self.fp8:
+            self._flush_value()
+        self.refresh_fwd_image()
+        bufs = self._eval_bufs.get(E)
+        if bufs is None:
+            bufs = self._eval_bufs[E] = (torch.zeros(E, dtype=torch.float32, device=self.device),
+                                         torch.zeros(E, dtype=torch.int32, device=self.device))
+        ret, length = bufs
+        e = self.env
+        k = eval_keys(self.p.seed)
+        limit = int(min(e.spec.time_limit, self.p.max_episode_length))
+        ints = [e.kind, E, self.O, self.A, e.state_dim, limit, 1 if self.p.std_convention == "var" else 0,
+                1 if deterministic else 0]
+        keys = [k["key_env"], k["key_term"], k["key_reset"], k["key_action"]]
+        self.ext.eval_rollout(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data,
+                              self.stats.mean_f32, self.stats.inv_std_f32, ret, length, ints, keys, self.qscale)
+        return ret, length
 
     @torch.no_grad()
     def values(self) -> None:

@@ -127,6 +127,18 @@ class TorchEngine:
     def current_obs(self) -> torch.Tensor:
         return self.obs
 
+    @torch.no_grad()
+    def evaluate(self, num_envs: int, deterministic: bool = False):
+        """Batched evaluation of the current policy under the current observation statistics on
+        fresh evaluation envs (runtime/evaluator.py evaluate_batch — the twin of the GPU engine's
+        kernel): ``(ret fp32 [E], len int32 [E])``.  Touches no training state."""
+        from .evaluator import evaluate_batch
+        if getattr(self.env, "host_stepped", False):
+            raise RuntimeError("evaluate() steps the builtin envs; a host-stepped (gym) env has no batched evaluation")
+        p = self.p
+        return evaluate_batch(self.model, self.stats, self.env.spec, num_envs, p.seed, p.max_episode_length,
+                              p.std_convention, deterministic)
+
     def env_state(self) -> Dict:
         return self.env.state_dict()
 

@@ -9,6 +9,10 @@ Here rank 0 hands the evaluator a consistent snapshot (reference-format state_di
 obs stats) every ``eval_every`` iterations through a bounded queue (dropped if the evaluator
 is busy — the trainer never blocks on it).  The evaluator runs on the CPU in its own process,
 keeps the print format, and never writes training state.
+
+``eval_mode="inline"`` replaces the process by a batched evaluation inside the trainer's engine
+(``csrc/eval.hip`` through ``HipEngine.evaluate``; runtime/launcher.py): ``evaluate_batch`` below
+is that kernel's torch twin — the CPU engine's path and the GPU tests' oracle.
 """
 from __future__ import annotations
 
@@ -45,6 +49,66 @@ def run_episode(model: ActorCritic, stats: RunningObsStats, env, key_action: int
             if bool(done[0]):
                 break
     return total, length
+
+
+EVAL_ENV_SEED_OFFSET = 7777   # the evaluator's env seed is Params.seed + this (evaluator_main)
+
+
+def eval_keys(seed: int) -> Dict[str, int]:
+    """RNG keys of an evaluation: the env streams of seed + 7777, rank 0 (as ``evaluator_main``
+    builds its env) and the evaluator's action stream of ``seed``."""
+    es = int(seed) + EVAL_ENV_SEED_OFFSET
+    return {"key_env": rng.base_key(es, rng.STREAM_ENV, 0), "key_term": rng.base_key(es, rng.STREAM_TERM, 0),
+            "key_reset": rng.base_key(es, rng.STREAM_RESET, 0),
+            "key_action": rng.base_key(int(seed), rng.STREAM_EVAL, 0)}
+
+
+@torch.no_grad()
+def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_envs: int, seed: int,
+                   max_episode_length: int, convention: str = "std", deterministic: bool = False):
+    """Batched evaluation, the torch twin of ``csrc/eval.hip``: ``num_envs`` fresh builtin envs
+    (seed ``seed + 7777``, rank 0; action key ``base_key(seed, STREAM_EVAL, 0)``) each run from
+    their reset to the end of their FIRST episode (terminal or time limit) under the frozen
+    ``stats``.  Finished envs keep stepping (and auto-resetting) in lockstep — the keys depend on
+    the shared step counter — but are masked out of the sums.
+
+    ``spec_or_env``: an ``EnvSpec``, or a builtin ``VecEnv`` of ``num_envs`` envs to use (reset
+    here).  Returns ``(ret fp32 [E], len int32 [E])``: the sum of the unclipped rewards, added in
+    step order in fp32 as ``VecEnv.ep_ret`` does, and the episode length."""
+    dev = model.flat.device
+    if hasattr(spec_or_env, "step"):
+        env = spec_or_env
+        if getattr(env, "host_stepped", False):
+            raise ValueError("evaluate_batch steps the builtin tensor envs, not a host-stepped (gym) env")
+        if env.E != int(num_envs):
+            raise ValueError(f"env has {env.E} envs, num_envs is {num_envs}")
+    else:
+        env = make_vec_env(spec_or_env, int(num_envs), seed=int(seed) + EVAL_ENV_SEED_OFFSET, rank=0, device=dev,
+                           max_episode_length=max_episode_length)
+    key_action = rng.base_key(int(seed), rng.STREAM_EVAL, 0)
+    E = env.E
+    obs = env.reset()
+    env.t = 0
+    ret = torch.zeros(E, dtype=torch.float32, device=env.device)
+    length = torch.zeros(E, dtype=torch.int32, device=env.device)
+    active = torch.ones(E, dtype=torch.bool, device=env.device)
+    dims = torch.arange(env.A, dtype=torch.int64, device=env.device)
+    for _ in range(env.limit):      # every first episode ends by step limit - 1
+        x = stats.normalize(obs.to(dev))
+        mu, log_std, _ = model(x)
+        if deterministic:
+            a = mu
+        else:
+            sig = torch.exp(log_std if convention == "std" else 0.5 * log_std)
+            eps = rng.gauss(key_action, env.env_idx[:, None], env.t, dims[None, :]).to(dev)
+            a = mu + sig * eps
+        obs, r, done, _ = env.step(a)
+        ret = torch.where(active, ret + r.to(torch.float32), ret)
+        length = torch.where(active, length + 1, length)
+        active = active & ~done
+        if not bool(active.any()):
+            break
+    return ret, length
 
 
 def evaluator_main(params_dict: Dict, q, stop_event=None, out_q=None) -> None:

@@ -52,7 +52,11 @@ def run_worker(params: Params, ctx: DistContext, max_iters: Optional[int] = None
         if hasattr(w.engine, "params_changed"):
             w.engine.params_changed()
     ev = None
-    if evaluator and ctx.is_main and params.eval_every > 0:
+    # eval_mode inline: rank 0 evaluates in its own engine (no evaluator process, no collective —
+    # the other ranks meet rank 0 at the next all-reduce as usual)
+    inline_eval = evaluator and ctx.is_main and params.eval_every > 0 and params.eval_mode == "inline"
+    w.quiet_eval = quiet
+    if evaluator and ctx.is_main and params.eval_every > 0 and params.eval_mode == "process":
         from .evaluator import EvaluatorHandle
         ev = EvaluatorHandle(params)
     history = []
@@ -79,11 +83,19 @@ def run_worker(params: Params, ctx: DistContext, max_iters: Optional[int] = None
             if ev is not None and w.iteration % params.eval_every == 0:
                 w.quiesce()     # a value step still on the side stream writes what the snapshot reads
                 ev.push(w.model.state_dict(), w.stats.state_dict(), w.iteration)
+            if inline_eval:
+                # an evaluation enqueued after the previous iteration is read now, one iteration
+                # later (the device has this iteration's work queued behind it: the host wait
+                # idles nothing); then this iteration's is enqueued
+                w.resolve_evals()
+                if w.iteration % params.eval_every == 0:
+                    w.stage_eval()
             if params.checkpoint_dir and params.checkpoint_every and w.iteration % params.checkpoint_every == 0:
                 save(w, ctx, params.checkpoint_dir)
             if max_iters is not None and n >= max_iters:
                 break
         record(w.finish_metrics())
+        w.resolve_evals()
         w.flush_pending()
         if params.checkpoint_dir:
             save(w, ctx, params.checkpoint_dir)

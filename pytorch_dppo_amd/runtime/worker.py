@@ -87,6 +87,10 @@ class DPPOWorker:
                 self._fault = (fi, fe)
         self._pending = None          # (async all-reduce work, extra) under --overlap-rollout
         self._staged = None           # metrics of the last deferred iteration (iteration_step(defer=True))
+        self._staged_evals: list = [] # inline evaluations enqueued, not yet read (stage_eval / resolve_evals)
+        self.eval_history: list = []  # their records, oldest first
+        self.quiet_eval = False       # no reference-format evaluation line on stdout
+        self._t_start = time.time()
         # GPU engine: optional side stream for the observation-statistics reduce + all-reduce +
         # merge (Params.stats_stream on, auto: when an all-reduce sits in that chain, off =
         # default).  Measured slower on the 1-GPU box: 26.06-26.35 vs 26.43-26.55 M env steps/s
@@ -325,6 +329,54 @@ class DPPOWorker:
             bad.append("obs_stats.mean")
         if bad:
             raise FloatingPointError(f"rank {self.ctx.rank} iteration {int(it)}: non-finite {bad}")
+
+    # -- inline evaluation (Params.eval_mode == "inline") ------------------------------------------
+    def stage_eval(self) -> None:
+        """Enqueue one batched evaluation of the current policy (engine.evaluate: csrc/eval.hip on
+        the GPU engine, its torch twin on the CPU one), reduce it on the device to [return mean,
+        std, min, max | length mean] and stage that vector into pinned host memory behind an
+        event — the pattern of ``_stage_metrics``: the host never waits here (every operand is a
+        device tensor: nothing is copied from host memory; the episode count is host-known).  No
+        collective: only the calling rank (rank 0) takes part."""
+        p = self.p
+        self.quiesce()       # the parameters are the synchronous ones, as for a snapshot
+        ret, length = self.engine.evaluate(p.eval_envs, bool(p.eval_deterministic))
+        r = ret.to(torch.float64)
+        vec = torch.stack([r.mean(), r.std(unbiased=False), r.min(), r.max(), length.to(torch.float64).mean()])
+        if self.device.type == "cuda":
+            host = torch.empty(vec.numel(), dtype=torch.float64, pin_memory=True)
+            host.copy_(vec, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        else:
+            host, ev = vec, None
+        self._staged_evals.append({"host": host, "event": ev, "iteration": self.iteration,
+                                   "episodes": int(ret.numel())})
+
+    def resolve_evals(self) -> list:
+        """The staged evaluations as records (oldest first): waits for their events through the
+        collective watchdog (``ctx.wait_event``), prints the reference's evaluator line
+        (test.py:56-59) on stdout unless ``quiet_eval`` and logs one JSONL record each — beside the
+        per-iteration records, not through them (the CSV columns are fixed)."""
+        staged, self._staged_evals = self._staged_evals, []
+        out = []
+        for st in staged:
+            if st["event"] is not None:
+                self.ctx.wait_event(st["event"])
+            if hasattr(self.engine, "raise_if_failed"):
+                self.engine.raise_if_failed()    # (behind a timed-out per-step filter launch: never report it)
+            v = st["host"].tolist()
+            rec = {"eval_iteration": int(st["iteration"]), "eval_return_mean": v[0], "eval_return_std": v[1],
+                   "eval_return_min": v[2], "eval_return_max": v[3], "eval_length_mean": v[4],
+                   "eval_episodes": st["episodes"]}
+            if not self.quiet_eval:
+                print("Time {}, episode reward {}, episode length {}".format(
+                    time.strftime("%Hh %Mm %Ss", time.gmtime(time.time() - self._t_start)), v[0], v[4]), flush=True)
+            if self.log is not None:
+                self.log.log_record(rec)
+            self.eval_history.append(rec)
+            out.append(rec)
+        return out
 
     def quiesce(self) -> None:
         """the GPU engine's deferred value-head step (side stream / pending all-reduce) applied:

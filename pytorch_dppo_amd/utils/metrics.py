@@ -122,6 +122,13 @@ class MetricsLogger:
                   f"av_reward {rec.get('mean_ep_return', float('nan')):.3f} "
                   f"loss {rec.get('loss', float('nan')):.4f}", flush=True)
 
+    def log_record(self, rec: Dict) -> None:
+        """a record beside the per-iteration ones (e.g. an inline evaluation): JSONL only — the
+        CSV columns and the stdout line belong to the iterations"""
+        if self.enabled and self.f:
+            self.f.write(json.dumps(rec) + "\n")
+            self.f.flush()
+
     def close(self) -> None:
         for name in ("f", "csv"):
             fh = getattr(self, name)
