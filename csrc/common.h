@@ -267,6 +267,48 @@ DEV void glds16(const void* g, void* lds) {
                                    (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
 
+// LDS fragment reads the compiler does not see (inline asm).  A read of LDS through C++ or a
+// builtin, next to in-flight LDS-DMA, makes hipcc wait for the DMA first (s_waitcnt vmcnt(0) in
+// front of every ds_read_b64_tr_b16 builtin: the whole ring drained); these carry no wait at all.
+// The caller issues a group of them back to back, then ONE settle statement — an asm
+// s_waitcnt lgkmcnt(0) that redefines the destination registers ("+v": no use moves above it) —
+// followed by __builtin_amdgcn_sched_barrier(0) (hipcc otherwise hoists register-only MFMAs over
+// an asm wait).  Used by csrc/phead.hip (tr4 / ph_settle) and csrc/wgrad.hip.
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+// the 32-bit LDS address of a pointer into shared memory
+DEV unsigned lds_addr(const void* p) {
+  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)(p);
+}
+// 4 consecutive rows x 16 columns of a row-major bf16 plane, transposed: lane 4 q + p of each
+// 16-lane group addresses row q, columns 4 p .. 4 p + 3; lane i receives column i (rows 0-3)
+DEV s16x4 tr4(const char* p) {
+  s16x4 v;
+  const unsigned addr = lds_addr(p);
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
+  return v;
+}
+// the same at LDS address addr + OFF (a compile-time instruction offset, < 64 KiB)
+template <int OFF>
+DEV s16x4 tr4_at(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
+  s16x4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
+  return v;
+}
+// 16 bytes per lane at LDS address addr + OFF (ds_read_b128)
+template <int OFF>
+DEV bf16x8 lds_rd16_at(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds offset field");
+  bf16x8 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "i"(OFF));
+  return v;
+}
+DEV bf16x8 cat8(s16x4 a0, s16x4 a1) {
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x8 v{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+  return *reinterpret_cast<const bf16x8*>(&v);
+}
+
 // s_waitcnt with only vmcnt constrained (gfx9 encoding: vmcnt[3:0] | expcnt[6:4]=7 |
 // lgkmcnt[11:8]=15 | vmcnt[5:4] in [15:14])
 #define WAIT_VMCNT(n) __builtin_amdgcn_s_waitcnt((((n) & 15) | (7 << 4) | (15 << 8) | ((((n) >> 4) & 3) << 14)))

@@ -52,17 +52,9 @@ static_assert(PH_WAVES * PH_XS * PH_XB <= PH_SCR / 2 && PH_WAVES * 32 * 32 * 4 <
 // read's 4-row group land in different 64-byte halves (conflict-free ds_read_b64_tr_b16)
 DEV int ph_swz(int row) { return ((row >> 1) & 1) << 2; }
 
-// 4 consecutive rows x 16 columns of a row-major bf16 plane, transposed: lane 4 q + p of each
-// 16-lane group addresses row q, columns 4 p .. 4 p + 3; lane i receives column i (rows 0-3)
-// (inline asm, no wait: with the builtin the compiler put an s_waitcnt vmcnt(0) — every in-flight
-// DMA and operand store — in front of these reads; ph_settle waits for them instead)
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-DEV s16x4 tr4(const char* p) {
-  s16x4 v;
-  const unsigned addr = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)(p);
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(addr));
-  return v;
-}
+// (tr4, the transposed 4-row LDS read in inline asm, and cat8: csrc/common.h.  With the builtin the
+// compiler put an s_waitcnt vmcnt(0) — every in-flight DMA and operand store — in front of these
+// reads; ph_settle waits for them instead)
 // the LDS reads of a group of fragments have landed (the asm redefines them: no use moves above)
 template <int DT>
 DEV void ph_settle(typename VT<DT>::Frag (&fa)[2], typename VT<DT>::Frag (&fb)[2]) {
@@ -73,11 +65,6 @@ DEV void ph_settle(typename VT<DT>::Frag (&fa)[2], typename VT<DT>::Frag (&fb)[2
   } else {
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]));
   }
-}
-DEV bf16x8 cat8(s16x4 a0, s16x4 a1) {
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x8 v{a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-  return *reinterpret_cast<const bf16x8*>(&v);
 }
 
 // dimension of accumulator register i of a 32x32 tile on lane half h (t32.h layout)

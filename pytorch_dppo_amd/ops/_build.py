@@ -58,9 +58,9 @@ def _digest(paths, extra: str) -> str:
     return h.hexdigest()[:16]
 
 
-def _compile(src: str, cflags, verbose: bool, csrc: str = CSRC, extra=()) -> str:
-    srcp = os.path.join(csrc, src)
-    deps = [srcp] + [os.path.join(csrc, h) for h in HEADERS]
+def device_flags(extra=()) -> list:
+    """The hipcc flags every csrc/*.hip is compiled with (tests that read a kernel's ISA compile
+    with exactly these, plus ``-S``)."""
     # -amdgpu-mfma-vgpr-form: MFMA accumulators in ordinary VGPRs (gfx90a+ unified register
     # file).  With AGPR accumulators the allocator shuffled them through VGPRs every loop turn
     # (~1,600 v_accvgpr_* in mlp_train, 96 per wgrad k-step pair); with it those copies vanish.
@@ -68,8 +68,13 @@ def _compile(src: str, cflags, verbose: bool, csrc: str = CSRC, extra=()) -> str
             "-mllvm", "-amdgpu-mfma-vgpr-form"]
     # A/B builds of compile-time variants (e.g. DPPO_EXTRA_CFLAGS="-DDPPO_X_CACHED"); the
     # flags enter the object cache key, so switching back rebuilds nothing stale
-    base += os.environ.get("DPPO_EXTRA_CFLAGS", "").split() + list(extra)
-    flags = base + cflags
+    return base + os.environ.get("DPPO_EXTRA_CFLAGS", "").split() + list(extra)
+
+
+def _compile(src: str, cflags, verbose: bool, csrc: str = CSRC, extra=()) -> str:
+    srcp = os.path.join(csrc, src)
+    deps = [srcp] + [os.path.join(csrc, h) for h in HEADERS]
+    flags = device_flags(extra) + cflags
     key = _digest(deps, " ".join(flags))
     obj = os.path.join(BUILD, f"{os.path.splitext(src)[0]}-{key}.o")
     if os.path.exists(obj):

@@ -3,7 +3,12 @@
 Arms run interleaved in ONE process on ONE worker (same box, same clocks): each round runs K
 deferred iterations per arm (the bench's production loop) and reports ms per iteration.
 
-    python scripts/ab_iter.py bf16x3 A,b,c [rounds] [iters]
+    python scripts/ab_iter.py bf16x3 A,b,c [rounds] [iters] [untimed rounds]
+
+(The first round of a process runs 0.1-0.15 ms per iteration above the later ones on every arm —
+clocks and caches still settling after the two warm-up iterations — so a max - min spread over
+the rounds is that ramp unless `untimed rounds` >= 1 lets it pass first; the default 0 keeps every
+round.)
 
 Arm names: "A" = the default build; a name of the table below = a runtime knob; any other name =
 the variant module _dppo_hip_<name> (ops/_build.py --variant <name> --define ...).  The engine
@@ -30,6 +35,7 @@ def main():
     want = sys.argv[2].split(",") if len(sys.argv) > 2 else ["x_cached", "x_stream"]
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 4
     iters = int(sys.argv[4]) if len(sys.argv) > 4 else 10
+    untimed = int(sys.argv[5]) if len(sys.argv) > 5 else 0
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ctx = init_single_rank_collective(dev, port=free_port())
@@ -73,7 +79,7 @@ def main():
         w.stats._refresh()
         eng.params_changed()
     res = {k: [] for k in want}
-    for _ in range(rounds):
+    for rnd in range(untimed + rounds):
         for k in want:
             (arms[k] if k in arms else (lambda k=k: use_ext(k)))()
             restore()
@@ -84,9 +90,11 @@ def main():
                 w.iteration_step(defer=True)
             torch.cuda.synchronize()
             w.finish_metrics()
-            res[k].append((time.perf_counter() - t0) / iters * 1e3)
-    out = {k: {"median_ms": sorted(v)[len(v) // 2], "all_ms": [round(x, 3) for x in v]} for k, v in res.items()}
-    print(json.dumps({"dtype": dtype, "arms": out}))
+            if rnd >= untimed:
+                res[k].append((time.perf_counter() - t0) / iters * 1e3)
+    out = {k: {"median_ms": sorted(v)[len(v) // 2], "spread_ms": round(max(v) - min(v), 3), "all_ms": [round(x, 3) for x in v]}
+           for k, v in res.items()}
+    print(json.dumps({"dtype": dtype, "untimed_rounds": untimed, "arms": out}))
     ctx.destroy()
 
 
