@@ -276,6 +276,68 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
   after_launch(__func__);
 }
 
+// One policy step for caller-supplied observations (csrc/act.hip): obs [E][O] fp32 -> actions [E][A],
+// logp [E], mu [E][A], x_out (E rows of d1 in the buffer precision, e.g. a slice of x_buf), mom
+// [ceil(E/16)][2][O] (overwritten with mom_init, else added to).  Every output is optional: an
+// empty tensor skips it; with none of actions / logp / mu the launch writes x_out / mom only.
+// ints: E,O,A,std_var,deterministic,mom_init; keys: action,e_base,step_key.
+void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales,
+                torch::Tensor flat, torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor obs,
+                torch::Tensor actions, torch::Tensor logp, torch::Tensor mu, torch::Tensor x_out, torch::Tensor mom,
+                std::vector<int64_t> ints, std::vector<int64_t> keys, torch::Tensor qscale) {
+  TORCH_CHECK(dt >= 0 && dt <= 3, "dt");
+  TORCH_CHECK(ints.size() == 6, "ints: E,O,A,std_var,deterministic,mom_init");
+  TORCH_CHECK(keys.size() == 3, "keys: action,e_base,step_key");
+  TORCH_CHECK(scales.size() >= 3, "scales");
+  Layout L = parse_layout(layout);
+  ActArgs a{};
+  TORCH_CHECK(ints[0] > 0 && ints[0] <= (int64_t)1 << 30, "E must be in [1, 2^30], got ", ints[0]);
+  TORCH_CHECK(ints[1] >= 1 && ints[1] < (int64_t)1 << 20 && ints[2] >= 1 && ints[2] < (int64_t)1 << 20, "O / A");
+  a.E = (int)ints[0]; a.O = (int)ints[1]; a.A = (int)ints[2];
+  a.std_var = ints[3] ? 1 : 0; a.deterministic = ints[4] ? 1 : 0; a.mom_init = ints[5] ? 1 : 0;
+  TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout / O / A mismatch");
+  TORCH_CHECK(L.d_in[1] > L.n_out[0] && L.d_in[2] > L.n_out[1], "layout: hidden widths");
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(keys[i] >= 0 && keys[i] <= (int64_t)UINT32_MAX, "keys must be 32-bit, got ", keys[i]);
+  auto given = [](const torch::Tensor& t) { return t.defined() && t.numel() > 0; };
+  const int nblk = (a.E + 15) / 16;
+  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
+  check(flat, "flat", at::kFloat, a.A);
+  check(mean, "mean", at::kFloat, a.O);
+  check(inv_std, "inv_std", at::kFloat, a.O);
+  check(obs, "obs", at::kFloat, (int64_t)a.E * a.O);
+  TORCH_CHECK(obs.numel() == (int64_t)a.E * a.O, "obs must have exactly E*O = ", (int64_t)a.E * a.O, " elements, got ",
+              obs.numel());
+  if (given(actions)) { check(actions, "actions", at::kFloat, (int64_t)a.E * a.A); a.actions = actions.data_ptr<float>(); }
+  if (given(logp)) { check(logp, "logp", at::kFloat, a.E); a.logp = logp.data_ptr<float>(); }
+  if (given(mu)) { check(mu, "mu", at::kFloat, (int64_t)a.E * a.A); a.mu = mu.data_ptr<float>(); }
+  if (given(x_out)) {
+    check(x_out, "x_out", storage_type(dt == 2 ? 1 : (int)dt), (int64_t)a.E * L.d_in[0]);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x_out.data_ptr()) % 16 == 0, "x_out must be 16-byte aligned");
+    a.x_out = x_out.data_ptr();
+  }
+  if (given(mom)) {
+    check(mom, "mom", at::kFloat, (int64_t)nblk * 2 * a.O);
+    check(shift, "shift", at::kFloat, a.O);
+    a.mom = mom.data_ptr<float>();
+    a.shift = shift.data_ptr<float>();
+  }
+  TORCH_CHECK(a.actions || a.logp || a.mu || a.x_out || a.mom, "policy_act: no output requested");
+  a.key_action = (uint32_t)keys[0]; a.e_base = (uint32_t)keys[1]; a.step_key = (uint32_t)keys[2];
+  a.W = wimg.data_ptr();
+  a.off_w1 = L.off_w[0]; a.off_w2 = L.off_w[1]; a.off_w3 = L.off_w[2];
+  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
+  a.n1 = L.n_out[0]; a.n2 = L.n_out[1]; a.n3 = L.n_out[2];
+  a.qscale = opt_scales(qscale);
+  a.s1 = (float)scales.at(0); a.s2 = (float)scales.at(1); a.s3 = (float)scales.at(2);
+  a.log_std = flat.data_ptr<float>();
+  a.mean = mean.data_ptr<float>();
+  a.inv_std = inv_std.data_ptr<float>();
+  a.obs = obs.data_ptr<float>();
+  launch_act((int)dt, a, cur_stream());
+  after_launch(__func__);
+}
+
 // the largest env-tile grid the per-step normalisation launch can run co-resident
 int64_t rollout_stepnorm_cap_b(int64_t dt, int64_t rows, std::vector<int64_t> layout, int64_t O, int64_t A, int64_t S) {
   Layout L = parse_layout(layout);
@@ -882,6 +944,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout", &rollout);
   m.def("rollout_stepnorm", &rollout_stepnorm);
   m.def("eval_rollout", &eval_rollout);
+  m.def("policy_act", &policy_act);
   m.def("rollout_stepnorm_cap", &rollout_stepnorm_cap_b);
   m.def("mlp_value", &mlp_value);
   m.def("mlp_train", &mlp_train);

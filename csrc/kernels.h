@@ -99,6 +99,37 @@ struct EvalArgs {
   int* len;            // [E] steps
 };
 
+// One policy step for caller-supplied observations (csrc/act.hip): E rows of raw fp32 observations
+// -> normalise -> policy MLP -> keyed Gaussian sample -> log-prob.  Every output is optional (null:
+// skipped); with none of actions / logp / mu the launch writes x_out / mom only (no MLP).
+struct ActArgs {
+  int E, O, A;         // rows, obs dims, act dims
+  int deterministic;   // 1: a = mu (eps = 0), 0: a = mu + sigma * eps
+  uint32_t key_action; // eps keyed (key_action, e_base + row, step_key)
+  uint32_t e_base, step_key;
+  // policy (packed weight image, storage precision): RolloutArgs' fields
+  const void* W;
+  int off_w1, off_w2, off_w3;
+  int d1, d2, d3;
+  int n1, n2, n3;
+  float s1, s2, s3;
+  const float* qscale;
+  const float* log_std;  // [A] fp32 master
+  int std_var;
+  // fixed observation normalisation
+  const float* mean;     // [O]
+  const float* inv_std;  // [O]
+  const float* shift;    // [O] the moments' shift (read only with mom)
+  const float* obs;      // [E][O] raw observations
+  // outputs
+  float* actions;      // [E][A]
+  float* logp;         // [E]
+  float* mu;           // [E][A]
+  void* x_out;         // [E][d1] buffer precision (XStore<DT>), row-major: e.g. a slice of x_buf
+  float* mom;          // [nblk][2][O] sum(obs - shift), sum((obs - shift)^2) per 16-row workgroup (RolloutArgs::mom)
+  int mom_init;        // != 0: mom is overwritten, 0: added to
+};
+
 // fp8 mode's gradient-amax ring (csrc/common.h Q8): [3 slots][4 tensors][Q8_SUB sub-slots][Q8_LINE]
 constexpr int Q8_SUB = 64, Q8_LINE = 32;
 constexpr int Q8_SLOT = 4 * Q8_SUB * Q8_LINE;   // dwords per ring slot
@@ -243,6 +274,7 @@ void launch_rollout(int dt, const RolloutArgs& a, int rows, hipStream_t s);
 void set_rollout_waves(int nw);                 // 4 or 8 waves per rollout workgroup (A/B)
 int rollout_stepnorm_cap(int dt, const RolloutArgs& a, int rows);   // co-resident grid of the SN launch
 void launch_eval(int dt, const EvalArgs& a, hipStream_t s);   // 16 envs per workgroup (csrc/eval.hip)
+void launch_act(int dt, const ActArgs& a, hipStream_t s);     // 16 rows per workgroup (csrc/act.hip)
 void launch_mlp_value(int dt, const MlpArgs& a, hipStream_t s);
 void launch_mlp_train(int dt, const MlpArgs& a, hipStream_t s);
 size_t mlp_train_lds_bytes(int dt, const MlpArgs& a);

@@ -45,6 +45,11 @@ class Params:
     # ---- MI355X-native additions --------------------------------------
     device: str = "cpu"                  # cpu | gpu
     env_backend: str = "builtin"         # builtin (tensor envs, in-kernel on GPU) | gym (gym.make, host-stepped)
+    host_policy: str = "torch"           # env_backend gym on the GPU engine, the per-step policy: torch (fp32 tensor
+                                         # ops: the path tests/test_gym_backend.py holds to the torch engine at 1e-6,
+                                         # so it stays the default and that test's reference) | kernel (one
+                                         # csrc/act.hip launch per step, buffer rows written in storage precision).
+                                         # Making kernel the default and retiring the torch path is a later change.
     num_envs: int = 1                    # E vectorised envs per worker
     dtype: str = "fp32"                  # fp32 | bf16x3 | bf16 | fp8  (GEMM operand precision;
                                          # bf16x3 = fp32-accurate split-bf16 on the bf16 MFMA)
@@ -135,6 +140,8 @@ class Params:
             raise ValueError(f"device must be cpu|gpu, got {self.device}")
         if self.env_backend not in ("builtin", "gym"):
             raise ValueError(f"env_backend must be builtin|gym, got {self.env_backend}")
+        if self.host_policy not in ("torch", "kernel"):
+            raise ValueError(f"host_policy must be torch|kernel, got {self.host_policy}")
         if self.dtype not in ("fp32", "bf16x3", "bf16", "fp8"):
             raise ValueError(f"dtype must be fp32|bf16x3|bf16|fp8, got {self.dtype}")
         if self.phead_fused_dw2 not in ("auto", "on", "off"):

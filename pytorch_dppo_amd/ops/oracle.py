@@ -10,6 +10,8 @@ from typing import Dict, Tuple
 
 import torch
 
+from ..utils import rng
+
 LOG_2PI = math.log(2.0 * math.pi)
 
 
@@ -24,6 +26,30 @@ def gaussian_logp(a: torch.Tensor, mu: torch.Tensor, log_std: torch.Tensor,
     log_sigma = log_std if convention == "std" else 0.5 * log_std
     z = (a - mu) * torch.exp(-log_sigma)
     return (-0.5 * z * z - 0.5 * LOG_2PI - log_sigma).sum(-1, keepdim=True)
+
+
+@torch.no_grad()
+def policy_act(model, stats, obs: torch.Tensor, key_action: int, env_idx: torch.Tensor, step_key: int,
+               convention: str = "std", deterministic: bool = False):
+    """One policy step for a batch of observations — the torch twin of ``csrc/act.hip``, the CPU
+    path of ``runtime/policy.PolicyRunner`` and the GPU tests' oracle.  The expressions are
+    ``TorchEngine.rollout``'s (normalise, policy forward, keyed noise, sample, log-prob), so a rollout
+    step and this function agree bit for bit.  ``deterministic``: ``a = mu`` and ``eps = 0``.
+
+    Returns ``(action [E,A], logp [E], mu [E,A], x [E,O])``."""
+    x = stats.normalize(obs)
+    mu, log_std, _ = model(x)
+    log_sigma = log_std if convention == "std" else 0.5 * log_std
+    if deterministic:
+        a = mu
+        logp = (-log_sigma.sum() - 0.5 * mu.shape[-1] * LOG_2PI).expand(mu.shape[0]).clone()
+        return a, logp, mu, x
+    sigma = torch.exp(log_sigma)
+    dims = torch.arange(mu.shape[-1], device=mu.device, dtype=torch.int64)
+    eps = rng.gauss(key_action, env_idx.to(mu.device)[:, None], step_key, dims[None, :])
+    a = mu + sigma * eps
+    logp = (-0.5 * eps * eps - 0.5 * LOG_2PI - log_sigma).sum(-1)
+    return a, logp, mu, x
 
 
 def gaussian_entropy(log_std: torch.Tensor, convention: str = "std") -> torch.Tensor:

@@ -159,6 +159,7 @@ class HipEngine:
         self._sn_epoch = 1         # its next granule tag (never reused)
         self._obs_scratch = None   # obs_observe partials + fp64 sums
         self._eval_bufs: Dict[int, tuple] = {}   # evaluate(): (ret, len) outputs per env count
+        self._act_bufs: Dict[int, tuple] = {}    # act(): (action, logp, mu) outputs per row count
         # ---- update geometry ----
         self.mb = params.minibatch_rows()
         # per-head streaming kernels (csrc/mlp_head.hip, 128 rows per workgroup): split-bf16 and
@@ -716,11 +717,15 @@ class HipEngine:
         """T steps of a host-stepped env (gym backend, train.py:82-106 vectorised): the env runs
         on the host, so the fused rollout kernel (which steps the builtin dynamics in-kernel)
         cannot; per step the E observations are normalised and the policy head evaluated as
-        device tensor ops (E rows; the env's host loop is the bottleneck here), the action noise
+        device tensor ops (E rows; ~126 small launches per step, ~0.8-1 ms: profiles/act/README.md), the action noise
         and log-prob use the same keyed RNG as the kernel, and the buffer rows are written in
         the storage precision.  The rollout-time x^T operand is not emitted (the update kernel
-        transposes X itself)."""
+        transposes X itself).  Params.host_policy = "kernel" takes _rollout_host_kernel instead
+        (one csrc/act.hip launch per step); this path stays the default and the reference of
+        tests/test_gym_backend.py (profiles/act/README.md times both)."""
         from ..ops import oracle
+        if self.p.host_policy == "kernel":
+            return self._rollout_host_kernel()
         p, T, E, O = self.p, self.T, self.E, self.O
         shift = self.stats.shift().clone()
         s1 = torch.zeros(O, dtype=torch.float64, device=self.device)
@@ -768,6 +773,52 @@ class HipEngine:
         self.x_buf.copy_(self.encode(X.view(-1, self.d0)))
         self._xT_valid = False
         return {"count": float(self.N), "s1": s1, "s2": s2, "shift": shift,
+                "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
+
+    @torch.no_grad()
+    def _rollout_host_kernel(self) -> Dict:
+        """_rollout_host with Params.host_policy = "kernel": per env step ONE csrc/act.hip launch
+        normalises the E observations, evaluates the policy on MFMA, samples with the keyed RNG and
+        writes actions / logp and the x_buf rows directly in storage precision, accumulating the
+        moments in ``self.mom``; then the host env step.  After the loop a rows-only launch writes
+        the bootstrap rows and one obs_reduce turns the moments into ``self.s12``.  No fp32 staging
+        tensor, no encode copy, no per-step torch moments / normalise / model / RNG ops."""
+        p, T, E, O = self.p, self.T, self.E, self.O
+        shift = self.stats.shift().clone()
+        # the host envs' episode sums stay in their own tensor: obs_reduce rewrites ep_sum from epstat
+        ep_ret, ep_cnt = 0.0, 0.0
+        norm = self.stats
+        if p.obs_norm_update == "step":
+            self.local_stats = RunningObsStats(O, self.device)
+            self.local_stats.copy_from(self.stats)
+            norm = self.local_stats
+        none = self.no_q
+        obs = self._host_obs.to(self.device, torch.float32).contiguous()
+        for t in range(T):
+            if p.obs_norm_update == "step":
+                self._observe_step(norm, obs, shift)
+            rows = slice(t * E, (t + 1) * E)
+            a = self.actions[rows]
+            self._launch_act(obs, self.env.t, False, 0, self.key_action, norm, shift, a, self.logp[rows], none,
+                             self.x_buf[rows], self.mom, t == 0)
+            nobs, r, done, info = self.env.step(a)
+            # the env's outputs are host tensors: clip / convert there, so each reaches its buffer
+            # rows as one upload and the act launch is the step's only kernel
+            if p.reward_clip > 0:
+                r = r.clamp(-p.reward_clip, p.reward_clip)
+            self.rewards[rows].copy_(r.to(torch.float32))
+            self.dones[rows].copy_(done.to(torch.float32))
+            ep_ret += float(info["ep_return_sum"])
+            ep_cnt += float(info["ep_count"])
+            obs = nobs.to(torch.float32).to(self.device).contiguous()
+        ep = torch.tensor([ep_ret, ep_cnt], dtype=torch.float64, device=self.device)
+        # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
+        self._launch_act(obs, self.env.t, False, 0, self.key_action, norm, shift, none, none, none,
+                         self.x_buf[T * E:], none, False)
+        self._host_obs = obs
+        self._xT_valid = False
+        self.ext.obs_reduce(self.mom, self.mom.shape[0], O, self.s12, self.epstat, self.ep_sum)
+        return {"count": float(self.N), "s1": self.s12[0], "s2": self.s12[1], "shift": shift,
                 "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
 
     @torch.no_grad()
@@ -885,6 +936,52 @@ class HipEngine:
         self.ext.eval_rollout(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data,
                               self.stats.mean_f32, self.stats.inv_std_f32, ret, length, ints, keys, self.qscale)
         return ret, length
+
+    def _launch_act(self, obs: torch.Tensor, step_key: int, deterministic: bool, e_base: int, key_action: int,
+                    norm: RunningObsStats, shift: torch.Tensor, actions: torch.Tensor, logp: torch.Tensor,
+                    mu: torch.Tensor, x_out: torch.Tensor, mom: torch.Tensor, mom_init: bool) -> None:
+        """one csrc/act.hip launch on the current stream (an empty tensor skips that output)"""
+        ints = [obs.shape[0], self.O, self.A, 1 if self.p.std_convention == "var" else 0, 1 if deterministic else 0,
+                1 if mom_init else 0]
+        keys = [key_action & 0xFFFFFFFF, e_base & 0xFFFFFFFF, step_key & 0xFFFFFFFF]
+        self.ext.policy_act(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data, norm.mean_f32,
+                            norm.inv_std_f32, shift, obs, actions, logp, mu, x_out, mom, ints, keys, self.qscale)
+
+    @torch.no_grad()
+    def act(self, obs: torch.Tensor, step_key: Optional[int] = None, deterministic: bool = False, e_base: int = 0, *,
+            x_out: Optional[torch.Tensor] = None, mom: Optional[torch.Tensor] = None, mom_init: bool = False,
+            key_action: Optional[int] = None):
+        """One policy step for caller-supplied observations (csrc/act.hip): ``obs`` fp32 ``[E', O]``
+        on the device, any ``E' >= 1`` (not tied to the engine's env count).  ONE launch on the
+        current stream, no host sync; returns the device tensors ``(action [E',A], logp [E'],
+        mu [E',A])`` this engine owns (rewritten by the next call for the same ``E'``).  The noise
+        of row r is keyed (``key_action``, ``e_base + r``, ``step_key``); ``step_key`` defaults to
+        the env's step counter, ``key_action`` to the engine's action stream.  ``x_out``: ``E'``
+        rows of ``d0`` in the buffer's storage precision (e.g. a slice of ``x_buf``) receive the
+        normalised rows; ``mom`` ``[ceil(E'/16), 2, O]`` fp32 the per-tile moments about the current
+        shift (overwritten with ``mom_init``, else added to).  Reads the policy image, log_std and
+        the stats; writes nothing but its outputs (no env state, buffers, stats, parameters or
+        optimizer state)."""
+        if obs.dim() != 2 or obs.shape[1] != self.O or obs.shape[0] < 1:
+            raise ValueError(f"obs must be [E, {self.O}], got {tuple(obs.shape)}")
+        if obs.device != self.device or obs.dtype != torch.float32:
+            raise ValueError("obs must be an fp32 tensor on the engine's device")
+        # as evaluate(): fp8's forward image follows the weights only through the refresh
+        if self.fp8:
+            self._flush_value()
+        self.refresh_fwd_image()
+        E = int(obs.shape[0])
+        bufs = self._act_bufs.get(E)
+        if bufs is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            bufs = self._act_bufs[E] = (torch.zeros(E, self.A, **f32), torch.zeros(E, **f32),
+                                        torch.zeros(E, self.A, **f32))
+        action, logp, mu = bufs
+        self._launch_act(obs.contiguous(), self.env.t if step_key is None else int(step_key), deterministic,
+                         int(e_base), self.key_action if key_action is None else int(key_action), self.stats,
+                         self.stats.shift(), action, logp, mu, self.empty_x if x_out is None else x_out,
+                         self.no_q if mom is None else mom, mom_init)
+        return action, logp, mu
 
     @torch.no_grad()
     def values(self) -> None:
