@@ -338,6 +338,52 @@ void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std
   after_launch(__func__);
 }
 
+// Episode bookkeeping of one step of a device-stepped tensor env (csrc/envstep.hip): E and S come
+// from state [E][S]; reward [E], terminal [E] (uint8 or bool), new_state / reset_state [E][S] are
+// read; state, ep_len [E] int32, ep_ret [E] are updated in place; rewards_row / dones_row [E] and
+// epstat [ceil(E/16)][2] (overwritten with init, else added to) are written.  Every extent is exact:
+// the grid is sized from E alone.
+void env_advance(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new_state, torch::Tensor reset_state,
+                 torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret, torch::Tensor rewards_row,
+                 torch::Tensor dones_row, torch::Tensor epstat, int64_t limit, double reward_clip, bool init) {
+  TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(1) >= 1, "state must be [E][S] with E, S >= 1");
+  const int64_t E = state.size(0), S = state.size(1);
+  TORCH_CHECK(E <= (int64_t)1 << 30 && S < (int64_t)1 << 20, "E must be <= 2^30 and S < 2^20, got ", E, " x ", S);
+  TORCH_CHECK(limit >= 1 && limit <= std::numeric_limits<int>::max(), "limit must be a positive int32, got ", limit);
+  const int64_t ntile = (E + ENVSTEP_TILE - 1) / ENVSTEP_TILE;
+  auto exact = [](const torch::Tensor& t, const char* name, at::ScalarType st, int64_t n) {
+    check(t, name, st, n);
+    TORCH_CHECK(t.numel() == n, name, " must have exactly ", n, " elements, got ", t.numel());
+  };
+  exact(reward, "reward", at::kFloat, E);
+  TORCH_CHECK(terminal.scalar_type() == at::kByte || terminal.scalar_type() == at::kBool,
+              "terminal has dtype ", terminal.scalar_type(), ", expected uint8 or bool");
+  exact(terminal, "terminal", terminal.scalar_type(), E);
+  exact(new_state, "new_state", at::kFloat, E * S);
+  exact(reset_state, "reset_state", at::kFloat, E * S);
+  exact(state, "state", at::kFloat, E * S);
+  exact(ep_len, "ep_len", at::kInt, E);
+  exact(ep_ret, "ep_ret", at::kFloat, E);
+  exact(rewards_row, "rewards_row", at::kFloat, E);
+  exact(dones_row, "dones_row", at::kFloat, E);
+  exact(epstat, "epstat", at::kFloat, ntile * 2);
+  EnvStepArgs a{};
+  a.E = (int)E; a.S = (int)S; a.limit = (int)limit;
+  a.reward_clip = (float)reward_clip; a.init = init ? 1 : 0;
+  a.reward = reward.data_ptr<float>();
+  a.terminal = static_cast<const unsigned char*>(terminal.data_ptr());
+  a.new_state = new_state.data_ptr<float>();
+  a.reset_state = reset_state.data_ptr<float>();
+  a.state = state.data_ptr<float>();
+  a.ep_len = ep_len.data_ptr<int>();
+  a.ep_ret = ep_ret.data_ptr<float>();
+  a.rewards_row = rewards_row.data_ptr<float>();
+  a.dones_row = dones_row.data_ptr<float>();
+  a.epstat = epstat.data_ptr<float>();
+  launch_env_advance(a, cur_stream());
+  after_launch(__func__);
+}
+
 // the largest env-tile grid the per-step normalisation launch can run co-resident
 int64_t rollout_stepnorm_cap_b(int64_t dt, int64_t rows, std::vector<int64_t> layout, int64_t O, int64_t A, int64_t S) {
   Layout L = parse_layout(layout);
@@ -945,6 +991,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout_stepnorm", &rollout_stepnorm);
   m.def("eval_rollout", &eval_rollout);
   m.def("policy_act", &policy_act);
+  m.def("env_advance", &env_advance);
   m.def("rollout_stepnorm_cap", &rollout_stepnorm_cap_b);
   m.def("mlp_value", &mlp_value);
   m.def("mlp_train", &mlp_train);

@@ -130,6 +130,30 @@ struct ActArgs {
   int mom_init;        // != 0: mom is overwritten, 0: added to
 };
 
+// Episode bookkeeping of ONE step of a device-stepped tensor env (csrc/envstep.hip): what
+// VecEnv.step does after the env's own dynamics, straight into the rollout buffer rows.  Per env
+// e < E: el = ep_len + 1, er = ep_ret + reward, done = terminal || el >= limit; on done the env's
+// 16-env tile gets (er, 1) and el = er = 0; state = done ? reset_state : new_state.
+constexpr int ENVSTEP_TILE = 16;   // envs per epstat entry: the rollout kernel's tile (RolloutArgs::epstat)
+struct EnvStepArgs {
+  int E, S;            // envs, state dims
+  int limit;           // episode step limit
+  float reward_clip;   // > 0: rewards_row = clamp(reward, +-reward_clip); ep_ret takes the unclipped reward
+  int init;            // != 0: epstat is overwritten, 0: added to (as ActArgs::mom_init)
+  const float* reward;              // [E] unclipped
+  const unsigned char* terminal;    // [E] 0 / 1
+  const float* new_state;           // [E][S]
+  const float* reset_state;         // [E][S]
+  // in / out
+  float* state;        // [E][S] (written only)
+  int* ep_len;         // [E]
+  float* ep_ret;       // [E]
+  // outputs
+  float* rewards_row;  // [E]
+  float* dones_row;    // [E] 0.f / 1.f
+  float* epstat;       // [ceil(E/16)][2] (finished-episode return sum, count) per tile
+};
+
 // fp8 mode's gradient-amax ring (csrc/common.h Q8): [3 slots][4 tensors][Q8_SUB sub-slots][Q8_LINE]
 constexpr int Q8_SUB = 64, Q8_LINE = 32;
 constexpr int Q8_SLOT = 4 * Q8_SUB * Q8_LINE;   // dwords per ring slot
@@ -275,6 +299,7 @@ void set_rollout_waves(int nw);                 // 4 or 8 waves per rollout work
 int rollout_stepnorm_cap(int dt, const RolloutArgs& a, int rows);   // co-resident grid of the SN launch
 void launch_eval(int dt, const EvalArgs& a, hipStream_t s);   // 16 envs per workgroup (csrc/eval.hip)
 void launch_act(int dt, const ActArgs& a, hipStream_t s);     // 16 rows per workgroup (csrc/act.hip)
+void launch_env_advance(const EnvStepArgs& a, hipStream_t s);   // 256 envs per workgroup (csrc/envstep.hip)
 void launch_mlp_value(int dt, const MlpArgs& a, hipStream_t s);
 void launch_mlp_train(int dt, const MlpArgs& a, hipStream_t s);
 size_t mlp_train_lds_bytes(int dt, const MlpArgs& a);

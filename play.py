@@ -16,7 +16,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from pytorch_dppo_amd.envs import get_spec, make_vec_env  # noqa: E402
+from pytorch_dppo_amd.envs import get_spec, import_env_module, make_vec_env  # noqa: E402
 from pytorch_dppo_amd.runtime.evaluator import EVAL_ENV_SEED_OFFSET  # noqa: E402
 from pytorch_dppo_amd.runtime.policy import PolicyRunner  # noqa: E402
 from pytorch_dppo_amd.utils import checkpoint  # noqa: E402
@@ -31,6 +31,7 @@ def main(argv=None):
     ap.add_argument("--episodes", type=int, default=1)
     ap.add_argument("--env-backend", choices=("builtin", "gym"), default=None)
     ap.add_argument("--env-name", default=None, help="default: the run's env")
+    ap.add_argument("--env-module", default=None, help="module that registers the env (default: the run's)")
     ap.add_argument("--deterministic", action="store_true", help="act with mu (the reference acts stochastically)")
     ns = ap.parse_args(argv)
 
@@ -39,6 +40,7 @@ def main(argv=None):
         raise FileNotFoundError(f"{ns.checkpoint}: no trainer_state.pt")
     cfg = st["config"]
     runner = PolicyRunner.from_checkpoint(ns.checkpoint, device=ns.device, dtype=ns.dtype)
+    import_env_module(ns.env_module if ns.env_module is not None else cfg.get("env_module", ""))
     name = ns.env_name or cfg["env_name"]
     backend = ns.env_backend or cfg.get("env_backend", "builtin")
     seed = int(cfg.get("seed", 1)) + EVAL_ENV_SEED_OFFSET

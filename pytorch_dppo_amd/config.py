@@ -44,7 +44,10 @@ class Params:
 
     # ---- MI355X-native additions --------------------------------------
     device: str = "cpu"                  # cpu | gpu
-    env_backend: str = "builtin"         # builtin (tensor envs, in-kernel on GPU) | gym (gym.make, host-stepped)
+    env_backend: str = "builtin"         # builtin (tensor envs: in-kernel on GPU when the rollout kernel knows the
+                                         # kind, device-stepped otherwise) | gym (gym.make, host-stepped)
+    env_module: str = ""                 # dotted module path imported once at start (worker, evaluator process,
+                                         # play.py) so that it can call envs.register_tensor_env; "" = none
     host_policy: str = "torch"           # env_backend gym on the GPU engine, the per-step policy: torch (fp32 tensor
                                          # ops: the path tests/test_gym_backend.py holds to the torch engine at 1e-6,
                                          # so it stays the default and that test's reference) | kernel (one

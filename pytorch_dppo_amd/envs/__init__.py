@@ -1,6 +1,9 @@
-from .registry import EnvSpec, get_spec, host_spec, known_envs, KIND_HOST, KIND_PENDULUM, KIND_SYNTHETIC
-from .vec_env import VecEnv, SyntheticEnv, PendulumEnv, make_vec_env
+from .registry import (EnvSpec, get_spec, host_spec, known_envs, register_tensor_env, import_env_module,
+                       KIND_HOST, KIND_PENDULUM, KIND_SYNTHETIC, KIND_TENSOR)
+from .vec_env import VecEnv, SyntheticEnv, PendulumEnv, CartPoleContinuousEnv, make_vec_env
 from .gym_adapter import GymVecEnv, gym_available, register_env
 
 __all__ = ["EnvSpec", "get_spec", "host_spec", "known_envs", "KIND_HOST", "KIND_PENDULUM", "KIND_SYNTHETIC",
-           "VecEnv", "SyntheticEnv", "PendulumEnv", "make_vec_env", "GymVecEnv", "gym_available", "register_env"]
+           "KIND_TENSOR", "register_tensor_env", "import_env_module",
+           "VecEnv", "SyntheticEnv", "PendulumEnv", "CartPoleContinuousEnv", "make_vec_env", "GymVecEnv",
+           "gym_available", "register_env"]

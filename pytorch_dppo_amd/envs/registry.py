@@ -7,6 +7,9 @@ env name resolves to
 * ``pendulum`` — a faithful vectorised Pendulum-v0 (gym's dynamics; CPU torch + HIP), or
 * ``synthetic`` — an obs/act-dim-faithful synthetic locomotion task (CPU torch + HIP),
   used for every MuJoCo/Bullet name, or
+* ``tensor`` — a ``VecEnv`` subclass registered with :func:`register_tensor_env` (by this package:
+  ``CartPoleContinuous-v1``; by a user's ``--env-module``): torch ops on device tensors, stepped on
+  the device by the GPU engine (``HipEngine.rollout_stepped``), or
 * ``gym`` — the real env through :mod:`pytorch_dppo_amd.envs.gym_adapter` with
   ``--env-backend gym`` (``gym.make``, or a factory installed with ``register_env``); its dims
   come from the env's spaces (:func:`host_spec`).
@@ -20,6 +23,8 @@ from dataclasses import dataclass
 KIND_SYNTHETIC = 0
 KIND_PENDULUM = 1
 KIND_HOST = 2          # a host-stepped env (gym backend): dims come from the env itself
+KIND_TENSOR = 3        # a registered tensor env (register_tensor_env): a VecEnv subclass the rollout kernel
+                       # does not know; the GPU engine steps it on the device (HipEngine.rollout_stepped)
 
 
 @dataclass(frozen=True)
@@ -32,6 +37,7 @@ class EnvSpec:
 
 
 _SPECS = {}
+_TENSOR_ENVS = {}      # name -> VecEnv subclass of the KIND_TENSOR specs
 
 
 def _reg(names, obs, act, kind, limit):
@@ -56,6 +62,39 @@ _reg(["AntBulletEnv-v0"], 28, 8, KIND_SYNTHETIC, 1000)
 def host_spec(name: str, obs_dim: int, act_dim: int, limit: int) -> EnvSpec:
     """spec of a host-stepped env (``--env-backend gym``) built from the env's own spaces"""
     return EnvSpec(name, int(obs_dim), int(act_dim), KIND_HOST, int(limit))
+
+
+def register_tensor_env(name: str, cls, obs_dim: int, act_dim: int, time_limit: int) -> EnvSpec:
+    """Register ``cls`` (a ``VecEnv`` subclass: ``state_dim``, ``_reset_state``, ``observe``,
+    ``_dynamics`` as torch ops on its device tensors) under ``name``; ``make_vec_env`` builds it for
+    the returned spec.  The names of the built-in table cannot be re-registered; registering the same
+    tensor env again (a module imported twice) replaces it."""
+    if name in _SPECS and _SPECS[name].kind != KIND_TENSOR:
+        raise ValueError(f"env {name!r} is a built-in entry and cannot be re-registered")
+    if name.startswith("Synthetic-"):
+        raise ValueError("the Synthetic-<obs>x<act> names are reserved")
+    if int(obs_dim) < 1 or int(act_dim) < 1 or int(time_limit) < 1:
+        raise ValueError("obs_dim, act_dim and time_limit must be positive")
+    spec = EnvSpec(name, int(obs_dim), int(act_dim), KIND_TENSOR, int(time_limit))
+    _SPECS[name] = spec
+    _TENSOR_ENVS[name] = cls
+    return spec
+
+
+def tensor_env_class(name: str):
+    """the class registered for a KIND_TENSOR spec"""
+    if name not in _TENSOR_ENVS:
+        raise KeyError(f"no tensor env registered as {name!r}; registered: {sorted(_TENSOR_ENVS)}")
+    return _TENSOR_ENVS[name]
+
+
+def import_env_module(module: str) -> None:
+    """``Params.env_module``: import a dotted module path once so that it can call
+    ``register_tensor_env`` (the worker, the evaluator process and play.py call this at start;
+    spawned processes do not inherit the parent's registrations).  Empty: nothing is imported."""
+    if module:
+        import importlib
+        importlib.import_module(module)
 
 
 def get_spec(name: str) -> EnvSpec:

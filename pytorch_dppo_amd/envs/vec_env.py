@@ -18,7 +18,7 @@ from typing import Dict, Tuple
 import torch
 
 from ..utils import rng
-from .registry import KIND_PENDULUM, KIND_SYNTHETIC, EnvSpec
+from .registry import KIND_PENDULUM, KIND_SYNTHETIC, KIND_TENSOR, EnvSpec, register_tensor_env, tensor_env_class
 
 SYN_DECAY = 0.9
 SYN_DRIVE = 0.1
@@ -183,16 +183,66 @@ class PendulumEnv(VecEnv):
         return torch.stack([newth, newthdot], 1), -costs, terminal
 
 
+class CartPoleContinuousEnv(VecEnv):
+    """Cart-pole with a continuous force: gym CartPole-v1's physics (Barto, Sutton & Anderson 1983
+    as gym integrates them: g = 9.8, cart 1.0, pole 0.1, pole half-length 0.5, explicit Euler,
+    dt = 0.02), the force ``10 * clamp(a, -1, 1)`` instead of the two discrete pushes.
+
+    state == observation (x, x_dot, theta, theta_dot).  Reward 1 per step; terminal when the NEW
+    state has |x| > 2.4 or |theta| > 12 degrees; reset draws every state dim uniform in +-0.05 from
+    the keyed reset stream (dims 0..3).  A registered tensor env (``CartPoleContinuous-v1``, kind
+    KIND_TENSOR): the rollout kernel does not know it, the GPU engine steps it on the device
+    (HipEngine.rollout_stepped)."""
+    GRAVITY, MASS_CART, MASS_POLE, HALF_LEN, FORCE_MAG, DT = 9.8, 1.0, 0.1, 0.5, 10.0, 0.02
+    X_LIMIT = 2.4
+    THETA_LIMIT = 12.0 * 2.0 * math.pi / 360.0
+    RESET_RANGE = 0.05
+
+    @property
+    def state_dim(self) -> int:
+        return 4
+
+    def _reset_state(self, step_key: int) -> torch.Tensor:
+        d = torch.arange(4, device=self.device, dtype=torch.int64)
+        u = rng.uniform01(rng.keyed(self.key_reset, self.env_idx[:, None], step_key, d[None, :]))
+        return (2.0 * u - 1.0) * self.RESET_RANGE
+
+    def observe(self) -> torch.Tensor:
+        return self.state.clone()
+
+    def _dynamics(self, a, step_key):
+        x, x_dot, th, th_dot = self.state.unbind(1)
+        force = self.FORCE_MAG * a[:, 0].clamp(-1.0, 1.0)
+        total_mass = self.MASS_CART + self.MASS_POLE
+        pml = self.MASS_POLE * self.HALF_LEN
+        cos, sin = torch.cos(th), torch.sin(th)
+        temp = (force + pml * th_dot * th_dot * sin) / total_mass
+        th_acc = (self.GRAVITY * sin - cos * temp) / (
+            self.HALF_LEN * (4.0 / 3.0 - self.MASS_POLE * cos * cos / total_mass))
+        x_acc = temp - pml * th_acc * cos / total_mass
+        new = torch.stack([x + self.DT * x_dot, x_dot + self.DT * x_acc,
+                           th + self.DT * th_dot, th_dot + self.DT * th_acc], 1)
+        terminal = (new[:, 0].abs() > self.X_LIMIT) | (new[:, 2].abs() > self.THETA_LIMIT)
+        return new, torch.ones(self.E, device=self.device, dtype=torch.float32), terminal
+
+
+register_tensor_env("CartPoleContinuous-v1", CartPoleContinuousEnv, obs_dim=4, act_dim=1, time_limit=500)
+
+
 def make_vec_env(spec: EnvSpec, num_envs: int, seed: int = 1, rank: int = 0, device="cpu",
                  max_episode_length: int = 10000, backend: str = "builtin", name: str = ""):
-    """``builtin``: the tensor envs above (stepped in-kernel on the GPU engine); ``gym``: real
-    gym envs stepped on the host (envs/gym_adapter.py, ``gym.make`` as main.py:45; ``name`` or
+    """``builtin``: the tensor envs above and the registered ones (``register_tensor_env``) — stepped
+    in-kernel on the GPU engine when the rollout kernel knows the kind, device-stepped otherwise;
+    ``gym``: real gym envs stepped on the host (envs/gym_adapter.py, ``gym.make`` as main.py:45; ``name`` or
     ``spec.name``)."""
     if backend == "gym":
         from .gym_adapter import GymVecEnv
         return GymVecEnv(name or spec.name, num_envs, seed=seed, rank=rank, max_episode_length=max_episode_length)
     if backend != "builtin":
         raise ValueError(f"env backend must be builtin|gym, got {backend!r}")
-    cls = PendulumEnv if spec.kind == KIND_PENDULUM else SyntheticEnv
+    if spec.kind == KIND_TENSOR:
+        cls = tensor_env_class(spec.name)
+    else:
+        cls = PendulumEnv if spec.kind == KIND_PENDULUM else SyntheticEnv
     return cls(spec, num_envs, seed=seed, rank=rank, device=device,
                max_episode_length=max_episode_length)

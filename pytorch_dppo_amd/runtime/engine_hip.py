@@ -27,6 +27,7 @@ from typing import Dict, Optional
 import torch
 
 from ..config import Params
+from ..envs.registry import KIND_PENDULUM, KIND_SYNTHETIC
 from ..models.actor_critic import ActorCritic, PackedLayout, fm_index
 from ..ops import native, storage
 from ..utils import rng
@@ -160,6 +161,7 @@ class HipEngine:
         self._obs_scratch = None   # obs_observe partials + fp64 sums
         self._eval_bufs: Dict[int, tuple] = {}   # evaluate(): (ret, len) outputs per env count
         self._act_bufs: Dict[int, tuple] = {}    # act(): (action, logp, mu) outputs per row count
+        self._eval_act_bufs: Dict[int, torch.Tensor] = {}   # evaluate() of a device-stepped env: its action rows
         # ---- update geometry ----
         self.mb = params.minibatch_rows()
         # per-head streaming kernels (csrc/mlp_head.hip, 128 rows per workgroup): split-bf16 and
@@ -343,6 +345,10 @@ class HipEngine:
         # host-stepped env (--env-backend gym): no in-kernel dynamics; rollout() takes the host
         # path (_rollout_host) and the update runs on the HIP kernels as usual
         self.host_env = bool(getattr(env, "host_stepped", False))
+        # a builtin (tensor) env of a kind the rollout / eval kernels do not run — a registered tensor
+        # env (envs.register_tensor_env): rollout() and evaluate() step it on the device instead
+        # (rollout_stepped: per step one act launch, the env's own torch ops, one env_advance launch)
+        self.stepped_env = not self.host_env and env.kind not in (KIND_SYNTHETIC, KIND_PENDULUM)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -822,11 +828,105 @@ class HipEngine:
                 "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
 
     @torch.no_grad()
+    def rollout_stepped(self) -> Dict:
+        """T steps of a builtin tensor env stepped ON THE DEVICE by its own torch ops — the path of a
+        registered tensor env (``stepped_env``), whose dynamics the rollout kernel does not know.
+        It also runs kinds 0 / 1 (the tests hold it against the fused kernel there).  Per step,
+        all on the current stream and with no host sync:
+
+          1. one csrc/act.hip launch: normalise ``obs``, policy MLP, keyed sample -> the step's
+             ``actions`` / ``logp`` / ``x_buf`` rows and the moments in ``self.mom`` (step key
+             ``env.t``, ``e_base`` 0, the engine's action key: the fused kernel's keys)
+          2. ``env._dynamics`` and ``env._reset_state``: the env's torch ops
+          3. one csrc/envstep.hip launch (``env_advance``): VecEnv.step's episode bookkeeping,
+             straight into the ``rewards`` / ``dones`` rows, ``env.state`` / ``ep_len`` / ``ep_ret``
+             (updated in place: they stay the env's live tensors, so ``env.state_dict()``
+             checkpoints them as ever) and ``self.epstat``
+          4. ``env.t += 1``, ``obs = env.observe()``
+
+        then a rows-only act launch for the bootstrap rows and one obs_reduce.  The update runs on
+        the usual kernels; the return dict is the other paths'."""
+        if self.host_env:
+            raise RuntimeError("rollout_stepped() steps a builtin tensor env on the device; a host-stepped (gym) env "
+                               "takes rollout()")
+        self._flush_value()        # (fp8: the refresh reads every layer; and the reduce rewrites ep_sum)
+        self.refresh_fwd_image()
+        p, T, E, O, env = self.p, self.T, self.E, self.O, self.env
+        norm = self.stats
+        if p.obs_norm_update == "step":
+            # as _rollout_host_kernel: every step's batch is merged into the worker-local stats
+            # (csrc/obs.hip, three launches) before the act launch normalises it
+            shift = self.stats.shift().clone()
+            norm = self.local_stats = RunningObsStats(O, self.device)
+            norm.copy_from(self.stats)
+        else:
+            shift = self.stats.shift()   # the fp32 mean itself, as the fused path (no snapshot copy)
+        none = self.no_q
+        clip = float(p.reward_clip)
+        if not env.state.is_contiguous():
+            env.state = env.state.contiguous()
+        obs = env.observe().to(torch.float32).contiguous()
+        for t in range(T):
+            if p.obs_norm_update == "step":
+                self._observe_step(norm, obs, shift)
+            rows = slice(t * E, (t + 1) * E)
+            a = self.actions[rows]
+            k = env.t & rng.MASK32
+            self._launch_act(obs, k, False, 0, self.key_action, norm, shift, a, self.logp[rows], none,
+                             self.x_buf[rows], self.mom, t == 0)
+            new_state, reward, terminal = env._dynamics(a, k)
+            reset_state = env._reset_state(k)
+            # (.to / .contiguous: no-ops for an env that returns fp32 / bool contiguous tensors)
+            self.ext.env_advance(reward.to(torch.float32).contiguous(), terminal.to(torch.bool).contiguous(),
+                                 new_state.to(torch.float32).contiguous(), reset_state.to(torch.float32).contiguous(),
+                                 env.state, env.ep_len, env.ep_ret, self.rewards[rows], self.dones[rows],
+                                 self.epstat, env.limit, clip, t == 0)
+            env.t += 1
+            obs = env.observe().to(torch.float32).contiguous()
+        # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
+        self._launch_act(obs, env.t, False, 0, self.key_action, norm, shift, none, none, none, self.x_buf[T * E:],
+                         none, False)
+        self._xT_valid = False
+        self.ext.obs_reduce(self.mom, self.mom.shape[0], O, self.s12, self.epstat, self.ep_sum)
+        return {"count": float(self.N), "s1": self.s12[0], "s2": self.s12[1], "shift": shift,
+                "ep_return_sum": self.ep_sum[0], "ep_count": self.ep_sum[1], "ep2": self.ep_sum}
+
+    @torch.no_grad()
+    def _evaluate_stepped(self, E: int, deterministic: bool):
+        """evaluate() of a device-stepped env: the torch twin's loop (evaluator.evaluate_batch: fresh
+        envs with the evaluator's keys, first-episode sums masked) with one csrc/act.hip launch as
+        its policy step and no early exit — ``limit`` steps, no host sync.  Writes nothing but its
+        own tensors (the envs are its own)."""
+        from ..envs import make_vec_env
+        from .evaluator import EVAL_ENV_SEED_OFFSET, eval_keys, evaluate_batch
+        p = self.p
+        env = make_vec_env(self.env.spec, E, seed=p.seed + EVAL_ENV_SEED_OFFSET, rank=0, device=self.device,
+                           max_episode_length=p.max_episode_length)
+        key_action = eval_keys(p.seed)["key_action"]
+        a = self._eval_act_bufs.get(E)
+        if a is None:
+            a = self._eval_act_bufs[E] = torch.zeros(E, self.A, dtype=torch.float32, device=self.device)
+        none = self.no_q
+
+        def act_fn(obs, step_key):
+            self._launch_act(obs.to(torch.float32).contiguous(), step_key, deterministic, 0, key_action, self.stats,
+                             self.stats.shift(), a, none, none, self.empty_x, none, False)
+            return a
+        return evaluate_batch(self.model, self.stats, env, E, p.seed, p.max_episode_length, p.std_convention,
+                              deterministic, act_fn=act_fn, early_exit=False)
+
+    @torch.no_grad()
     def rollout(self, stats_stream: Optional[torch.cuda.Stream] = None) -> Dict:
         """T env steps for every env.  ``stats_stream`` (rollout-mode obs stats only): the
         one-launch moment/episode-stat reduce runs there, ordered after the rollout kernel, so
         it (and the caller's merge, issued on the same stream) overlaps the value forward and
         the update; the caller orders its stream after that work before reading the stats."""
+        if self.stepped_env:
+            ro = self.rollout_stepped()
+            if stats_stream is not None:
+                # as the host path below: the caller merges on stats_stream, after this rollout's work
+                stats_stream.wait_stream(torch.cuda.current_stream(self.device))
+            return ro
         # fp8: the weights changed during the previous update (Adam rewrites only the bf16 image);
         # before either path, so values() / GAE of a host-env rollout see the current weights too.
         # The refresh reads every layer: a value step still running on the side stream
@@ -908,7 +1008,9 @@ class HipEngine:
         stream), each from its reset to the end of its first episode, under the current fp32
         images of ``self.stats``.  ONE launch on the current stream, no host sync; returns the
         device tensors ``(ret fp32 [E], len int32 [E])`` this engine owns (rewritten by the next
-        call for the same ``num_envs``).  Reads the policy image, log_std and the stats; writes
+        call for the same ``num_envs``).  A device-stepped env (``stepped_env``) has no in-kernel
+        dynamics: _evaluate_stepped runs the same evaluation as a device-stepped loop, still without
+        a host sync.  Reads the policy image, log_std and the stats; writes
         nothing but its own outputs (no env state, buffers, stats, parameters or optimizer state)."""
         from .evaluator import eval_keys
         if self.host_env:
@@ -922,6 +1024,8 @@ class HipEngine:
         if self.fp8:
             self._flush_value()
         self.refresh_fwd_image()
+        if self.stepped_env:
+            return self._evaluate_stepped(E, bool(deterministic))
         bufs = self._eval_bufs.get(E)
         if bufs is None:
             bufs = self._eval_bufs[E] = (torch.zeros(E, dtype=torch.float32, device=self.device),

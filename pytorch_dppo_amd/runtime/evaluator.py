@@ -22,7 +22,7 @@ from typing import Dict, Optional
 
 import torch
 
-from ..envs import get_spec, host_spec, make_vec_env
+from ..envs import get_spec, host_spec, import_env_module, make_vec_env
 from ..models.actor_critic import ActorCritic
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
@@ -65,7 +65,8 @@ def eval_keys(seed: int) -> Dict[str, int]:
 
 @torch.no_grad()
 def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_envs: int, seed: int,
-                   max_episode_length: int, convention: str = "std", deterministic: bool = False):
+                   max_episode_length: int, convention: str = "std", deterministic: bool = False,
+                   act_fn=None, early_exit: bool = True):
     """Batched evaluation, the torch twin of ``csrc/eval.hip``: ``num_envs`` fresh builtin envs
     (seed ``seed + 7777``, rank 0; action key ``base_key(seed, STREAM_EVAL, 0)``) each run from
     their reset to the end of their FIRST episode (terminal or time limit) under the frozen
@@ -74,7 +75,13 @@ def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_
 
     ``spec_or_env``: an ``EnvSpec``, or a builtin ``VecEnv`` of ``num_envs`` envs to use (reset
     here).  Returns ``(ret fp32 [E], len int32 [E])``: the sum of the unclipped rewards, added in
-    step order in fp32 as ``VecEnv.ep_ret`` does, and the episode length."""
+    step order in fp32 as ``VecEnv.ep_ret`` does, and the episode length.
+
+    ``act_fn(obs, step_key) -> actions [E, A]``: the policy step, in place of the torch one below
+    (``model``, ``stats``, ``convention`` and ``deterministic`` are then its business;
+    HipEngine.evaluate passes one ``csrc/act.hip`` launch).  ``early_exit=False`` drops the
+    ``active.any()`` break — the loop's only host sync — and runs all ``limit`` steps; the masked
+    sums are the same."""
     dev = model.flat.device
     if hasattr(spec_or_env, "step"):
         env = spec_or_env
@@ -94,19 +101,22 @@ def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_
     active = torch.ones(E, dtype=torch.bool, device=env.device)
     dims = torch.arange(env.A, dtype=torch.int64, device=env.device)
     for _ in range(env.limit):      # every first episode ends by step limit - 1
-        x = stats.normalize(obs.to(dev))
-        mu, log_std, _ = model(x)
-        if deterministic:
-            a = mu
+        if act_fn is not None:
+            a = act_fn(obs, env.t)
         else:
-            sig = torch.exp(log_std if convention == "std" else 0.5 * log_std)
-            eps = rng.gauss(key_action, env.env_idx[:, None], env.t, dims[None, :]).to(dev)
-            a = mu + sig * eps
+            x = stats.normalize(obs.to(dev))
+            mu, log_std, _ = model(x)
+            if deterministic:
+                a = mu
+            else:
+                sig = torch.exp(log_std if convention == "std" else 0.5 * log_std)
+                eps = rng.gauss(key_action, env.env_idx[:, None], env.t, dims[None, :]).to(dev)
+                a = mu + sig * eps
         obs, r, done, _ = env.step(a)
         ret = torch.where(active, ret + r.to(torch.float32), ret)
         length = torch.where(active, length + 1, length)
         active = active & ~done
-        if not bool(active.any()):
+        if early_exit and not bool(active.any()):
             break
     return ret, length
 
@@ -115,6 +125,7 @@ def evaluator_main(params_dict: Dict, q, stop_event=None, out_q=None) -> None:
     from ..config import Params
     p = Params.from_dict(params_dict)
     torch.set_num_threads(1)
+    import_env_module(p.env_module)   # this is a spawned process: the user's registrations are made here
     if p.env_backend == "gym":   # test.py:28 gym.make
         env = make_vec_env(None, 1, seed=p.seed + 7777, rank=0, max_episode_length=p.max_episode_length,
                            backend="gym", name=p.env_name)

@@ -26,7 +26,7 @@ from typing import Dict, Optional
 import torch
 
 from ..config import Params
-from ..envs import get_spec, host_spec, make_vec_env
+from ..envs import get_spec, host_spec, import_env_module, make_vec_env
 from ..models.actor_critic import ActorCritic
 from ..parallel.dist import DistContext
 from ..utils import rng
@@ -47,6 +47,7 @@ class DPPOWorker:
         self.p = params
         self.ctx = ctx
         self.device = ctx.device
+        import_env_module(params.env_module)    # a user's register_tensor_env calls (spawned ranks too)
         if params.env_backend == "gym":
             # real gym envs (main.py:45 / train.py:48): dims from the env's own spaces
             self.env = make_vec_env(None, params.num_envs, seed=params.seed, rank=ctx.rank,
