@@ -1,13 +1,13 @@
 // Policy inference kernel: ONE policy step for E caller-supplied observations.
 //
-// The rollout kernel's per-step pipeline (csrc/rollout.hip) without its env: the observations come
-// from the caller (a host-stepped env, a served request batch), not from in-kernel physics.  Each
-// workgroup owns ROWS rows; per row r < E:
+// The rollout kernel's per-step pipeline (csrc/policy_step.h, the code csrc/rollout.hip runs)
+// without its env: the observations come from the caller (a host-stepped env, a served request
+// batch), not from in-kernel physics.  Each workgroup owns ROWS rows; per row r < E:
 //   (a) raw fp32 obs[r][0..O) from global memory -> x = clamp((obs - mean) * inv_std, -5, 5), the
 //       constant 1 at column O, zeros up to d1 -> LDS tile (the rollout's observe phase); with `mom`
 //       the workgroup's sum(obs - shift) / sum((obs - shift)^2) over its valid rows
 //   (b) x_out: the tile's rows in the buffer precision (XStore<DT>), as 16-byte row chunks
-//   (c) policy MLP on MFMA (mlp_core.h layer_gemm, the rollout's precisions and scales)
+//   (c) policy MLP on MFMA (the rollout's precisions and scales)
 //   (d) a = mu + sigma * eps, eps keyed (action key, e_base + r, step_key), one Box-Muller pair per
 //       two action dims; deterministic: a = mu, eps = 0
 //   (e) logp = sum_j(-0.5 eps_j^2 - log sigma_j) - 0.5 A log(2 pi)
@@ -16,72 +16,51 @@
 // tile are computed and never stored.  The kernel reads the policy image, log_std, the stats and
 // obs; its only global stores are the outputs listed in ActArgs.  No atomics: a workgroup owns its
 // rows and its moment slice (overwritten or added to, stream order), so a launch is deterministic.
-#include <type_traits>
-
-#include "kernels.h"
-#include "mlp_core.h"
+#include "policy_step.h"
 
 namespace {
 
-constexpr float LOG_2PI_F = 1.8378770664093453f;
+// the launch's dynamic LDS: the kernel's pointers and the host's byte count from one carve
+template <int DT, int ROWS>
+struct ActLds {
+  using XB = typename Prec<XStore<DT>::DTX>::T;
+  LdsCarve cv;
+  PolicyTiles<DT> t;
+  float* epsb;     // [ROWS][A] the action noise
+  float* lsg;      // [log sigma | sigma]
+  uint32_t* kes;   // per-row (env, step) key prefix of the action noise
+  XB* xsb;         // fp8: bf16 staging tile of the buffer rows (policy_step.h store_tile_rows)
+  __host__ __device__ ActLds(char* smem, const ActArgs& a)
+      : cv(smem), t(cv, a.net, ROWS, a.A), epsb(cv.take<float>(ROWS * a.A)), lsg(cv.take<float>(2 * a.A)),
+        kes(cv.take<uint32_t>(ROWS)), xsb(DT == DT_FP8 ? cv.take<XB>(ROWS * a.net.d1) : nullptr) {}
+};
 
 template <int DT, int ROWS, int NW>
 __global__ __launch_bounds__(NW * 64) void act_kernel(ActArgs a) {
   using P = Prec<DT>;
-  using T = typename P::T;
+  using PX = Prec<XStore<DT>::DTX>;
   constexpr int NTHR = 64 * NW;
   static_assert(ROWS % 4 == 0 && NTHR % ROWS == 0 && (NTHR / ROWS) <= 64, "act tiling");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e0 = blockIdx.x * ROWS;
   const int nvalid = min(ROWS, a.E - e0);
-  const int O = a.O, A = a.A;
-  const int ld1 = Lds<DT>::stride(a.d1), ld2 = Lds<DT>::stride(a.d2), ld3 = Lds<DT>::stride(a.d3);
+  const int O = a.O, A = a.A, d1 = a.net.d1;
   const bool det = a.deterministic != 0;
   // (kernel arguments: every branch on them is workgroup-uniform)
   const bool mlp = a.actions != nullptr || a.logp != nullptr || a.mu != nullptr;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  LdsCarve cv(smem);
-  T* xs = cv.take<T>(ROWS * ld1);
-  T* h1 = cv.take<T>(ROWS * ld2);
-  T* h2 = cv.take<T>(ROWS * ld3);
-  float* mu = cv.take<float>(ROWS * A);
-  float* epsb = cv.take<float>(ROWS * A);
-  float* lsg = cv.take<float>(2 * A);             // per action dim: log sigma [0, A), sigma [A, 2A)
-  uint32_t* kes = cv.take<uint32_t>(ROWS);        // per-row (env, step) key prefix of the action noise
-  // fp8: the MFMA tile is e4m3 but the buffer rows are bf16 (csrc/rollout.hip: a bf16 staging tile
-  // lets them leave as 16-byte row chunks)
-  using PX = Prec<XStore<DT>::DTX>;
-  using XB = typename PX::T;
-  constexpr bool STAGE = DT == DT_FP8;
-  XB* xsb = STAGE ? cv.take<XB>(ROWS * a.d1) : nullptr;
-
-  const T* W = reinterpret_cast<const T*>(a.W);
-  const T* W1 = W + a.off_w1;
-  const T* W2 = W + a.off_w2;
-  const T* W3 = W + a.off_w3;
-  const float sc1 = a.qscale ? a.qscale[0] : a.s1;
-  const float sc2 = a.qscale ? a.qscale[1] : a.s2;
-  const float sc3 = a.qscale ? a.qscale[2] : a.s3;
+  const ActLds<DT, ROWS> L(smem, a);
+  PolicyStep<DT, ROWS, NW> ps(a.net, L.t);
 
   if (mlp) {
-    preset_pad<DT>(h1, ld2, ROWS, a.n1, tid, NTHR);   // the layers' epilogues write columns < n
-    preset_pad<DT>(h2, ld3, ROWS, a.n2, tid, NTHR);
-    for (int j = tid; j < A; j += NTHR) {
-      const float ls = a.log_std[j];
-      const float lsig = a.std_var ? 0.5f * ls : ls;
-      lsg[j] = lsig;
-      lsg[A + j] = __expf(lsig);
-    }
+    ps.setup(L.lsg, tid);
     // hashed here, published by the observe phase's barrier
-    if (tid >= NTHR - ROWS) {
-      const int r = tid - (NTHR - ROWS);
-      kes[r] = key_es(a.key_action, a.e_base + (uint32_t)(e0 + r), a.step_key);
-    }
+    key_prefixes<ROWS, NTHR>(L.kes, {a.key_action}, a.e_base + (uint32_t)e0, a.step_key, tid);
   }
 
   // ---- (a) observe, moments, normalise -> LDS tile: thread = feature (coalesced obs rows) ----
-  for (int d = tid; d < a.d1; d += NTHR) {
+  for (int d = tid; d < d1; d += NTHR) {
     float m = 0.f, is = 1.f, sh = 0.f;
     if (d < O) {
       m = a.mean[d];
@@ -98,12 +77,12 @@ __global__ __launch_bounds__(NW * 64) void act_kernel(ActArgs a) {
         const float dd = r < nvalid ? o - sh : 0.f;
         ls1 += dd;
         ls2 += dd * dd;
-        xv = fminf(fmaxf((o - m) * is, -5.f), 5.f);
+        xv = norm_clamp(o, m, is);
       } else {
-        xv = (d == O) ? 1.f : 0.f;
+        xv = pad_col(d, O);
       }
-      P::put(xs, r * ld1 + d, xv);
-      if constexpr (STAGE) xsb[r * a.d1 + d] = PX::cvt(xv);
+      P::put(L.t.xs, r * L.t.ld1 + d, xv);
+      if constexpr (DT == DT_FP8) L.xsb[r * d1 + d] = PX::cvt(xv);
     }
     if (a.mom != nullptr && d < O) {
       // this workgroup's slice [2][O] of the RolloutArgs::mom layout, owned by thread d
@@ -118,55 +97,25 @@ __global__ __launch_bounds__(NW * 64) void act_kernel(ActArgs a) {
       }
     }
   }
-  BPre<DT, ROWS / 16> pf;   // cross-barrier weight prefetch of each layer's first k-chunk
-  if (mlp) layer_prefetch<DT, ROWS, NW>(pf, W1, a.d1, a.n1, wave, lane);
+  if (mlp) ps.prefetch(wave, lane);
   __syncthreads();
-  // ---- (b) row-major buffer rows from the normalised LDS tile: one 16-byte store per 16 bytes of
-  // features (split-bf16: the LDS tile and the buffer share the 32-byte hi|lo group layout) ----
-  if (a.x_out != nullptr) {
-    XB* xo = reinterpret_cast<XB*>(a.x_out);
-    constexpr int EPC = 16 / sizeof(XB);
-    const int ch = a.d1 / EPC;
-    for (int i = tid; i < nvalid * ch; i += NTHR) {
-      const int r = i / ch, c = i - r * ch;
-      const void* src = STAGE ? static_cast<const void*>(xsb + r * a.d1 + c * EPC)
-                              : static_cast<const void*>(xs + r * ld1 + c * EPC);
-      *reinterpret_cast<uint4*>(xo + (size_t)(e0 + r) * a.d1 + c * EPC) = *reinterpret_cast<const uint4*>(src);
-    }
-  }
+  // ---- (b) row-major buffer rows from the normalised LDS tile ----
+  if (a.x_out != nullptr)
+    store_tile_rows<DT, NTHR>(reinterpret_cast<typename PX::T*>(a.x_out) + (size_t)e0 * d1, L.t, L.xsb, d1, nvalid, tid);
   if (!mlp) return;
   // ---- (c) policy MLP ----
-  layer_gemm<DT, ROWS, NW, EPI_TANH, true>(xs, ld1, a.d1, W1, a.n1, h1, ld2, sc1, wave, lane, nullptr, 0, 0, 0, &pf);
-  layer_prefetch<DT, ROWS, NW>(pf, W2, a.d2, a.n2, wave, lane);
-  __syncthreads();
-  layer_gemm<DT, ROWS, NW, EPI_TANH, true>(h1, ld2, a.d2, W2, a.n2, h2, ld3, sc2, wave, lane, nullptr, 0, 0, 0, &pf);
-  layer_prefetch<DT, ROWS, NW>(pf, W3, a.d3, a.n3, wave, lane);
-  __syncthreads();
-  layer_gemm<DT, ROWS, NW, EPI_LINEAR_F32, true>(h2, ld3, a.d3, W3, a.n3, mu, A, sc3, wave, lane, nullptr, 0, 0, 0,
-                                                 &pf);
-  __syncthreads();
-  // ---- (d) sample a = mu + sigma * eps (one Box-Muller pair -> two action dims) ----
-  const int npa = (A + 1) >> 1;
-  for (int i = tid; i < ROWS * npa; i += NTHR) {
-    const int r = i / npa, q = i - r * npa;
-    float2 g = make_float2(0.f, 0.f);
-    if (!det) g = gauss_pair(kes[r], (uint32_t)q);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = 2 * q + h;
-      if (j < A) {
-        const float eps = h ? g.y : g.x;
-        const float mv = mu[r * A + j];
-        const float av = det ? mv : mv + lsg[A + j] * eps;   // deterministic: the action IS mu
-        epsb[r * A + j] = eps;
-        if (r < nvalid) {
-          const size_t o = (size_t)(e0 + r) * A + j;
-          if (a.actions != nullptr) a.actions[o] = av;
-          if (a.mu != nullptr) a.mu[o] = mv;
-        }
-      }
+  ps.layers(wave, lane);
+  // ---- (d) sample a = mu + sigma * eps ----
+  sample_loop<ROWS, NTHR>(L.kes, A, tid, !det, [&](int r, int j, float eps) {
+    const float mv = L.t.mu[r * A + j];
+    const float av = det ? mv : mv + L.lsg[A + j] * eps;   // deterministic: the action IS mu
+    L.epsb[r * A + j] = eps;
+    if (r < nvalid) {
+      const size_t o = (size_t)(e0 + r) * A + j;
+      if (a.actions != nullptr) a.actions[o] = av;
+      if (a.mu != nullptr) a.mu[o] = mv;
     }
-  }
+  });
   if (a.logp == nullptr) return;
   __syncthreads();
   // ---- (e) logp: LPE lanes per row (contiguous inside a wave) share the dims, reduce by shuffles ----
@@ -174,46 +123,22 @@ __global__ __launch_bounds__(NW * 64) void act_kernel(ActArgs a) {
     constexpr int LPE = NTHR / ROWS;
     const int r = tid / LPE, l = tid - r * LPE;
     float lp = 0.f;
-    for (int j = l; j < A; j += LPE) {
-      const float ep = epsb[r * A + j];
-      lp += -0.5f * ep * ep - lsg[j];
-    }
+    for (int j = l; j < A; j += LPE) lp += logp_term(L.epsb[r * A + j], L.lsg[j]);
 #pragma unroll
     for (int o = LPE / 2; o > 0; o >>= 1) lp += __shfl_xor(lp, o, LPE);
-    if (l == 0 && r < nvalid) a.logp[e0 + r] = lp - 0.5f * LOG_2PI_F * (float)A;
+    if (l == 0 && r < nvalid) a.logp[e0 + r] = lp - logp_const(A);
   }
-}
-
-template <int DT, int ROWS>
-size_t act_lds(const ActArgs& a) {
-  auto al = [](size_t b) { return (b + 15) & ~size_t(15); };
-  using T = typename Prec<DT>::T;
-  size_t b = 0;
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d1));
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d2));
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d3));
-  b += 2 * al(sizeof(float) * ROWS * a.A);
-  b += al(sizeof(float) * 2 * a.A);
-  b += al(sizeof(uint32_t) * ROWS);
-  if (DT == DT_FP8) b += al(sizeof(typename Prec<XStore<DT>::DTX>::T) * ROWS * a.d1);
-  return b;
-}
-
-template <int DT, int ROWS, int NW>
-void launch_nw(const ActArgs& a, hipStream_t s) {
-  const size_t lds = act_lds<DT, ROWS>(a);
-  const int nblk = (a.E + ROWS - 1) / ROWS;
-  if (lds > 65536) set_max_lds_once<act_kernel<DT, ROWS, NW>>(lds);
-  hipLaunchKernelGGL((act_kernel<DT, ROWS, NW>), dim3(nblk), dim3(NW * 64), lds, s, a);
-  HIP_CHECK_LAUNCH();
 }
 
 }  // namespace
 
-// the rollout's launch forms: 8 waves for bf16x3 / bf16 / fp8, 4 for fp32 (twice the fragment registers)
+// the rollout's launch forms (policy_step.h POLICY_WAVES), 16 rows per workgroup
 extern "C" void launch_act(int dt, const ActArgs& a, hipStream_t s) {
-  if (dt == DT_F32) launch_nw<DT_F32, 16, 4>(a, s);
-  else if (dt == DT_BF16) launch_nw<DT_BF16, 16, 8>(a, s);
-  else if (dt == DT_S3) launch_nw<DT_S3, 16, 8>(a, s);
-  else launch_nw<DT_FP8, 16, 8>(a, s);
+  dispatch_dt(dt, [&](auto d) {
+    constexpr int DT = decltype(d)::value, ROWS = 16, NW = POLICY_WAVES<DT, ROWS>;
+    const size_t lds = ActLds<DT, ROWS>(nullptr, a).cv.off;
+    if (lds > 65536) set_max_lds_once<act_kernel<DT, ROWS, NW>>(lds);
+    hipLaunchKernelGGL((act_kernel<DT, ROWS, NW>), dim3((a.E + ROWS - 1) / ROWS), dim3(NW * 64), lds, s, a);
+    HIP_CHECK_LAUNCH();
+  });
 }

@@ -100,6 +100,24 @@ int64_t wimg_extent(const Layout& L) {
   return mx;
 }
 
+// The policy fields of RolloutArgs / EvalArgs / ActArgs, filled and checked in one place
+PolicyNet policy_net(int64_t dt, const Layout& L, const torch::Tensor& wimg, const std::vector<double>& scales,
+                     const torch::Tensor& flat, int64_t A, int64_t std_var, const torch::Tensor& qscale) {
+  TORCH_CHECK(L.d_in[1] > L.n_out[0] && L.d_in[2] > L.n_out[1], "layout: hidden widths");
+  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
+  check(flat, "flat", at::kFloat, A);
+  PolicyNet n{};
+  n.W = wimg.data_ptr();
+  n.off_w1 = L.off_w[0]; n.off_w2 = L.off_w[1]; n.off_w3 = L.off_w[2];
+  n.d1 = L.d_in[0]; n.d2 = L.d_in[1]; n.d3 = L.d_in[2];
+  n.n1 = L.n_out[0]; n.n2 = L.n_out[1]; n.n3 = L.n_out[2];
+  n.qscale = opt_scales(qscale);
+  n.s1 = (float)scales.at(0); n.s2 = (float)scales.at(1); n.s3 = (float)scales.at(2);
+  n.log_std = flat.data_ptr<float>();
+  n.std_var = (int)std_var;
+  return n;
+}
+
 // ------------------------------------------------------------------------------------------
 RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
                          torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
@@ -114,7 +132,7 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   RolloutArgs a{};
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.T = (int)ints[5]; a.t_base = (int)ints[6]; a.buf_E = (int)ints[7]; a.t0 = (uint32_t)ints[8];
-  a.limit = (int)ints[9]; a.std_var = (int)ints[10];
+  a.limit = (int)ints[9];
   TORCH_CHECK(a.E > 0 && a.T >= 1 && a.buf_E == a.E, "bad E/T");
   TORCH_CHECK(a.kind == 0 || a.kind == 1, "kind");
   TORCH_CHECK(a.kind == 0 ? a.S == a.O : (a.S == 2 && a.O == 3), "state dims");
@@ -123,8 +141,7 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   check(state, "state", at::kFloat, (int64_t)a.E * a.S);
   check(ep_len, "ep_len", at::kInt, a.E);
   check(ep_ret, "ep_ret", at::kFloat, a.E);
-  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
-  check(flat, "flat", at::kFloat, a.A);
+  a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[10], qscale);
   check(mean, "mean", at::kFloat, a.O);
   check(inv_std, "inv_std", at::kFloat, a.O);
   check(shift, "shift", at::kFloat, a.O);
@@ -141,13 +158,6 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   a.state = state.data_ptr<float>();
   a.ep_len = ep_len.data_ptr<int>();
   a.ep_ret = ep_ret.data_ptr<float>();
-  a.W = wimg.data_ptr();
-  a.off_w1 = L.off_w[0]; a.off_w2 = L.off_w[1]; a.off_w3 = L.off_w[2];
-  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
-  a.n1 = L.n_out[0]; a.n2 = L.n_out[1]; a.n3 = L.n_out[2];
-  a.qscale = opt_scales(qscale);
-  a.s1 = (float)scales.at(0); a.s2 = (float)scales.at(1); a.s3 = (float)scales.at(2);
-  a.log_std = flat.data_ptr<float>();
   a.mean = mean.data_ptr<float>();
   a.inv_std = inv_std.data_ptr<float>();
   a.shift = shift.data_ptr<float>();
@@ -245,14 +255,12 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
   TORCH_CHECK(ints[1] > 0 && ints[1] <= (int64_t)1 << 30, "E must be in [1, 2^30], got ", ints[1]);
   TORCH_CHECK(ints[5] >= 1 && ints[5] <= (int64_t)1 << 20, "limit must be in [1, 2^20], got ", ints[5]);
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
-  a.limit = (int)ints[5]; a.std_var = ints[6] ? 1 : 0; a.deterministic = ints[7] ? 1 : 0;
+  a.limit = (int)ints[5]; a.deterministic = ints[7] ? 1 : 0;
   TORCH_CHECK(a.kind == 0 || a.kind == 1, "kind");
   TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
   TORCH_CHECK(a.kind == 0 ? a.S == a.O : (a.S == 2 && a.O == 3), "state dims");
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
-  TORCH_CHECK(L.d_in[1] > L.n_out[0] && L.d_in[2] > L.n_out[1], "layout: hidden widths");
-  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
-  check(flat, "flat", at::kFloat, a.A);
+  a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[6] ? 1 : 0, qscale);
   check(mean, "mean", at::kFloat, a.O);
   check(inv_std, "inv_std", at::kFloat, a.O);
   check(ret, "ret", at::kFloat, a.E);
@@ -261,13 +269,6 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
               ret.numel(), " / ", len.numel());
   a.key_env = (uint32_t)keys[0]; a.key_term = (uint32_t)keys[1]; a.key_reset = (uint32_t)keys[2];
   a.key_action = (uint32_t)keys[3];
-  a.W = wimg.data_ptr();
-  a.off_w1 = L.off_w[0]; a.off_w2 = L.off_w[1]; a.off_w3 = L.off_w[2];
-  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
-  a.n1 = L.n_out[0]; a.n2 = L.n_out[1]; a.n3 = L.n_out[2];
-  a.qscale = opt_scales(qscale);
-  a.s1 = (float)scales.at(0); a.s2 = (float)scales.at(1); a.s3 = (float)scales.at(2);
-  a.log_std = flat.data_ptr<float>();
   a.mean = mean.data_ptr<float>();
   a.inv_std = inv_std.data_ptr<float>();
   a.ret = ret.data_ptr<float>();
@@ -294,15 +295,13 @@ void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std
   TORCH_CHECK(ints[0] > 0 && ints[0] <= (int64_t)1 << 30, "E must be in [1, 2^30], got ", ints[0]);
   TORCH_CHECK(ints[1] >= 1 && ints[1] < (int64_t)1 << 20 && ints[2] >= 1 && ints[2] < (int64_t)1 << 20, "O / A");
   a.E = (int)ints[0]; a.O = (int)ints[1]; a.A = (int)ints[2];
-  a.std_var = ints[3] ? 1 : 0; a.deterministic = ints[4] ? 1 : 0; a.mom_init = ints[5] ? 1 : 0;
+  a.deterministic = ints[4] ? 1 : 0; a.mom_init = ints[5] ? 1 : 0;
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout / O / A mismatch");
-  TORCH_CHECK(L.d_in[1] > L.n_out[0] && L.d_in[2] > L.n_out[1], "layout: hidden widths");
   for (int i = 0; i < 3; ++i)
     TORCH_CHECK(keys[i] >= 0 && keys[i] <= (int64_t)UINT32_MAX, "keys must be 32-bit, got ", keys[i]);
   auto given = [](const torch::Tensor& t) { return t.defined() && t.numel() > 0; };
   const int nblk = (a.E + 15) / 16;
-  check(wimg, "wimg", storage_type((int)dt), wimg_extent(L));
-  check(flat, "flat", at::kFloat, a.A);
+  a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[3] ? 1 : 0, qscale);
   check(mean, "mean", at::kFloat, a.O);
   check(inv_std, "inv_std", at::kFloat, a.O);
   check(obs, "obs", at::kFloat, (int64_t)a.E * a.O);
@@ -324,13 +323,6 @@ void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std
   }
   TORCH_CHECK(a.actions || a.logp || a.mu || a.x_out || a.mom, "policy_act: no output requested");
   a.key_action = (uint32_t)keys[0]; a.e_base = (uint32_t)keys[1]; a.step_key = (uint32_t)keys[2];
-  a.W = wimg.data_ptr();
-  a.off_w1 = L.off_w[0]; a.off_w2 = L.off_w[1]; a.off_w3 = L.off_w[2];
-  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
-  a.n1 = L.n_out[0]; a.n2 = L.n_out[1]; a.n3 = L.n_out[2];
-  a.qscale = opt_scales(qscale);
-  a.s1 = (float)scales.at(0); a.s2 = (float)scales.at(1); a.s3 = (float)scales.at(2);
-  a.log_std = flat.data_ptr<float>();
   a.mean = mean.data_ptr<float>();
   a.inv_std = inv_std.data_ptr<float>();
   a.obs = obs.data_ptr<float>();
@@ -389,7 +381,7 @@ int64_t rollout_stepnorm_cap_b(int64_t dt, int64_t rows, std::vector<int64_t> la
   Layout L = parse_layout(layout);
   RolloutArgs a{};
   a.O = (int)O; a.A = (int)A; a.S = (int)S;
-  a.d1 = L.d_in[0]; a.d2 = L.d_in[1]; a.d3 = L.d_in[2];
+  a.net.d1 = L.d_in[0]; a.net.d2 = L.d_in[1]; a.net.d3 = L.d_in[2];
   a.sn_g1 = reinterpret_cast<unsigned long long*>(1);   // (only selects the LDS size of the SN kernel)
   return (int64_t)::rollout_stepnorm_cap((int)dt, a, (int)rows);
 }

@@ -1,0 +1,179 @@
+// The in-kernel envs' physics, written once: the rollout kernel (csrc/rollout.hip) and the
+// evaluation kernel (csrc/eval.hip) both step their envs with these, so the two are bit-equal by
+// construction and both are held to the same torch env (envs/vec_env.py).  kind 0: the synthetic
+// S = O dim env; kind 1: the pendulum (state (th, thdot), obs (cos th, sin th, thdot)).
+// The env state is a [ROWS][S] fp32 tile in LDS; `act` the [ROWS][A] actions of the step.
+#pragma once
+#include <type_traits>
+
+#include "kernels.h"
+#include "mlp_core.h"
+
+constexpr float SYN_DECAY = 0.9f, SYN_DRIVE = 0.1f, SYN_NOISE = 0.05f, SYN_RESET = 0.1f;
+constexpr float SYN_TERM_P = 0.002f;
+constexpr float ENV_PI = 3.14159265358979f, ENV_2PI = 6.28318530717959f;
+constexpr uint32_t RESET_STEP_KEY = 0xFFFFFFFFu;   // VecEnv.reset()'s step key
+
+// observation of env r, dim d.  KIND is a template parameter: with a runtime kind the
+// pendulum's libm cosf/sinf (Payne-Hanek reduction, divergent per lane) was inlined into each
+// of the ROWS unrolled iterations of the synthetic env's observe loop (~2,500 dead
+// instructions per step and a 3x slower phase).
+template <int KIND>
+DEV float env_obs(const float* st, int S, int r, int d) {
+  if constexpr (KIND == 1) {  // pendulum: (cos th, sin th, thdot)
+    const float th = st[r * S + 0];
+    return d == 0 ? cosf(th) : (d == 1 ? sinf(th) : st[r * S + 1]);
+  } else {
+    return st[r * S + d];
+  }
+}
+// f(integral_constant<int, kind>): the caller's loop body compiled once per kind
+template <typename F>
+DEV void env_kind_switch(int kind, F&& f) {
+  if (kind == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
+
+// synthetic dynamics, per state dim d: drive weight and driving action index (LDS tables filled
+// once per launch: no per-step modulo)
+DEV void syn_tables(float* wdrv, int* jdx, int S, int A, int tid, int nthr) {
+  for (int d = tid; d < S; d += nthr) {
+    wdrv[d] = 0.5f + (float)(d % 7) / 7.0f;
+    jdx[d] = d % A;
+  }
+}
+
+// synthetic reward: 1 - mean_j (clamp(a_j) - tanh(s_j))^2 over j < min(A, O); one term of the sum
+DEV float syn_err_term(float av, float sv) {
+  const float ac = fminf(fmaxf(av, -1.f), 1.f);
+  const float d = ac - fast_tanh(sv);
+  return d * d;
+}
+// unclipped reward and termination of env e (tile row r) for this step's action; err: the
+// synthetic env's sum of syn_err_term over its na dims (unused by the pendulum)
+DEV float env_reward(int kind, const float* st, int S, const float* act, int A, int r, float err, int na,
+                     uint32_t key_term, uint32_t e, uint32_t kstep, bool& term) {
+  term = false;
+  if (kind == 1) {
+    float th = st[r * S], thd = st[r * S + 1];
+    float u = fminf(fmaxf(act[r * A], -2.f), 2.f);
+    float thn = fmodf(th + ENV_PI, ENV_2PI);
+    if (thn < 0.f) thn += ENV_2PI;
+    thn -= ENV_PI;
+    return -(thn * thn + 0.1f * thd * thd + 0.001f * u * u);
+  }
+  term = uniform01(keyed(key_term, e, kstep, 0u)) < SYN_TERM_P;
+  return 1.f - err / (float)na;
+}
+
+// pendulum reset of tile row r (env e) keyed (reset key, e, step)
+DEV void pend_reset(float* st, int S, int r, uint32_t key_reset, uint32_t e, uint32_t step) {
+  float u0 = uniform01(keyed(key_reset, e, step, 0u));
+  float u1 = uniform01(keyed(key_reset, e, step, 1u));
+  st[r * S] = (2.f * u0 - 1.f) * ENV_PI;
+  st[r * S + 1] = 2.f * u1 - 1.f;
+}
+DEV void pend_step(float* st, int S, int r, float a0) {
+  float th = st[r * S], thd = st[r * S + 1];
+  float u = fminf(fmaxf(a0, -2.f), 2.f);
+  float nthd = thd + (-3.f * 10.f / 2.f * sinf(th + ENV_PI) + 3.f * u) * 0.05f;
+  float nth = th + nthd * 0.05f;
+  nthd = fminf(fmaxf(nthd, -8.f), 8.f);
+  st[r * S] = nth;
+  st[r * S + 1] = nthd;
+}
+
+// synthetic item = (row, dim pair p): one Box-Muller pair gives the two dims' noise
+struct SynItem {
+  float st0, st1, a0, a1, w0, w1;
+  uint32_t key;
+  bool done, has1;
+  int d0;
+};
+// done: the in-place reset (SYN_RESET * noise), else the transition
+DEV void syn_item_next(const SynItem& q, int p, float& n0, float& n1) {
+  const float2 g = gauss_pair(q.key, (uint32_t)p);
+  if (q.done) {
+    n0 = SYN_RESET * g.x;
+    n1 = SYN_RESET * g.y;
+  } else {
+    const float a0 = fminf(fmaxf(q.a0, -1.f), 1.f);
+    const float a1 = fminf(fmaxf(q.a1, -1.f), 1.f);
+    n0 = SYN_DECAY * q.st0 + SYN_DRIVE * fast_tanh(q.w0 * a0) + SYN_NOISE * g.x;
+    n1 = SYN_DECAY * q.st1 + SYN_DRIVE * fast_tanh(q.w1 * a1) + SYN_NOISE * g.y;
+  }
+}
+
+// State transition of the whole tile, with the in-place reset of the rows whose done_s is set.
+// kes: this step's per-row key prefixes [env | reset] at kes[ROWS + r] / kes[2 ROWS + r].  The
+// caller's barriers separate it from the writers of act / done_s / kes and the readers of st.
+template <int ROWS, int NTHR>
+DEV void env_transition(int kind, float* st, int S, const float* act, int A, const float* done_s,
+                        const uint32_t* kes, const float* wdrv, const int* jdx, uint32_t key_reset, int e0,
+                        uint32_t kstep, int tid) {
+  if (kind == 1) {
+    if (tid < ROWS) {
+      if (done_s[tid] > 0.5f) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
+      else pend_step(st, S, tid, act[tid * A]);
+    }
+    return;
+  }
+  // consecutive threads on consecutive pairs of one row: the ROWS x S/2 items spread evenly over
+  // the threads and the per-dim constants come from the LDS tables.  Two items per turn with
+  // every LDS read of both issued before any state store (items never share a state slot),
+  // so the second item's loads, hashes and transcendentals overlap the first's instead of
+  // waiting behind its stores; the reset / step choice is a select, not a branch.
+  const int np = (S + 1) >> 1;
+  int r = tid / np, p = tid - r * np;
+  const int sr = NTHR / np, sp = NTHR - sr * np;
+  auto load = [&](int rr, int pp) {
+    SynItem q;
+    q.d0 = 2 * pp;
+    q.has1 = q.d0 + 1 < S;
+    const int d1 = q.has1 ? q.d0 + 1 : q.d0;
+    q.done = done_s[rr] > 0.5f;
+    q.key = q.done ? kes[2 * ROWS + rr] : kes[ROWS + rr];
+    q.st0 = st[rr * S + q.d0];
+    q.st1 = st[rr * S + d1];
+    q.a0 = act[rr * A + jdx[q.d0]];
+    q.a1 = act[rr * A + jdx[d1]];
+    q.w0 = wdrv[q.d0];
+    q.w1 = wdrv[d1];
+    return q;
+  };
+  while (r < ROWS) {
+    int r2 = r + sr, p2 = p + sp;
+    if (p2 >= np) { p2 -= np; ++r2; }
+    const bool v2 = r2 < ROWS;
+    const SynItem q1 = load(r, p);
+    const SynItem q2 = load(v2 ? r2 : r, v2 ? p2 : p);   // past the end: re-read item 1 (unused)
+    float n10, n11, n20, n21;
+    syn_item_next(q1, p, n10, n11);
+    syn_item_next(q2, v2 ? p2 : p, n20, n21);
+    st[r * S + q1.d0] = n10;
+    if (q1.has1) st[r * S + q1.d0 + 1] = n11;
+    if (v2) {
+      st[r2 * S + q2.d0] = n20;
+      if (q2.has1) st[r2 * S + q2.d0 + 1] = n21;
+    }
+    r = r2 + sr;
+    p = p2 + sp;
+    if (p >= np) { p -= np; ++r; }
+  }
+}
+
+// Fresh envs for every row of the tile, as VecEnv.reset() (step key RESET_STEP_KEY)
+template <int ROWS, int NTHR>
+DEV void env_reset_fresh(int kind, float* st, int S, uint32_t key_reset, int e0, int tid) {
+  if (kind == 1) {
+    if (tid < ROWS) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), RESET_STEP_KEY);
+    return;
+  }
+  const int np = (S + 1) >> 1;
+  for (int i = tid; i < ROWS * np; i += NTHR) {
+    const int r = i / np, p = i - r * np;
+    const float2 g = gauss_pair(key_es(key_reset, (uint32_t)(e0 + r), RESET_STEP_KEY), (uint32_t)p);
+    st[r * S + 2 * p] = SYN_RESET * g.x;
+    if (2 * p + 1 < S) st[r * S + 2 * p + 1] = SYN_RESET * g.y;
+  }
+}

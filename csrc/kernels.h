@@ -4,6 +4,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The three-layer policy of the rollout / eval / act kernels (csrc/policy_step.h): the packed weight
+// image in the storage precision and the Gaussian head's log_std.  bindings.cpp policy_net() fills
+// and checks it for all three.
+struct PolicyNet {
+  const void* W;
+  int off_w1, off_w2, off_w3;
+  int d1, d2, d3;      // padded input widths of the 3 layers (P32(K+1))
+  int n1, n2, n3;      // real output widths (H1, H2, A)
+  float s1, s2, s3;    // dequant scales (fp8; 1 otherwise)
+  const float* qscale; // optional device array of the 6 per-layer dequant scales (overrides s*)
+  const float* log_std;  // [A] fp32 master
+  int std_var;         // 1: exp(log_std) is the variance (reference DPPO), 0: it is sigma
+};
+
 struct RolloutArgs {
   // env (state lives in global memory between launches, in LDS during the launch)
   int kind;            // 0 synthetic, 1 pendulum
@@ -17,15 +31,7 @@ struct RolloutArgs {
   float* state;        // [E][S]
   int* ep_len;         // [E]
   float* ep_ret;       // [E]
-  // policy (packed weight image, storage precision)
-  const void* W;
-  int off_w1, off_w2, off_w3;
-  int d1, d2, d3;      // padded input widths of the 3 layers (P32(K+1))
-  int n1, n2, n3;      // real output widths (H1, H2, A)
-  float s1, s2, s3;    // dequant scales (fp8; 1 otherwise)
-  const float* qscale; // optional device array of the 6 per-layer dequant scales (overrides s*)
-  const float* log_std;  // [A] fp32 master
-  int std_var;         // 1: exp(log_std) is the variance (reference DPPO), 0: it is sigma
+  PolicyNet net;
   // observation normalisation
   const float* mean;
   const float* inv_std;
@@ -82,15 +88,7 @@ struct EvalArgs {
   int limit;           // episode step limit (the launch's loop bound)
   int deterministic;   // 1: a = mu, 0: a = mu + sigma * eps (eps keyed: action key, env, step)
   uint32_t key_env, key_term, key_reset, key_action;
-  // policy (packed weight image, storage precision): RolloutArgs' fields
-  const void* W;
-  int off_w1, off_w2, off_w3;
-  int d1, d2, d3;
-  int n1, n2, n3;
-  float s1, s2, s3;
-  const float* qscale;
-  const float* log_std;  // [A] fp32 master
-  int std_var;
+  PolicyNet net;
   // fixed observation normalisation
   const float* mean;     // [O]
   const float* inv_std;  // [O]
@@ -107,15 +105,7 @@ struct ActArgs {
   int deterministic;   // 1: a = mu (eps = 0), 0: a = mu + sigma * eps
   uint32_t key_action; // eps keyed (key_action, e_base + row, step_key)
   uint32_t e_base, step_key;
-  // policy (packed weight image, storage precision): RolloutArgs' fields
-  const void* W;
-  int off_w1, off_w2, off_w3;
-  int d1, d2, d3;
-  int n1, n2, n3;
-  float s1, s2, s3;
-  const float* qscale;
-  const float* log_std;  // [A] fp32 master
-  int std_var;
+  PolicyNet net;
   // fixed observation normalisation
   const float* mean;     // [O]
   const float* inv_std;  // [O]

@@ -388,12 +388,15 @@ DEV void layer_gemm(const typename Prec<DT>::T* __restrict__ A, int lda, int kdi
 __host__ __device__ inline size_t al16(size_t b) { return (b + 15) & ~size_t(15); }
 
 // 16-byte aligned carve of the dynamic LDS region (Guideline 17: keep the base 16-B aligned).
+// On the host with a null base it only measures: a kernel whose carve is a host/device function
+// gets its launch's dynamic-LDS bytes (`off` afterwards) from the code that places its pointers,
+// which are not dereferenced there.
 struct LdsCarve {
   char* base;
   size_t off;
-  DEV explicit LdsCarve(char* b) : base(b), off(0) {}
+  __host__ __device__ __forceinline__ explicit LdsCarve(char* b) : base(b), off(0) {}
   template <typename T>
-  DEV T* take(size_t n) {
+  __host__ __device__ __forceinline__ T* take(size_t n) {
     T* p = reinterpret_cast<T*>(base + off);
     off += (n * sizeof(T) + 15) & ~size_t(15);
     return p;

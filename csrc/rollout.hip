@@ -10,31 +10,16 @@
 // here: V(s_t) for GAE is computed afterwards by one big batched forward over all (T+1)*E
 // rows (mlp.hip), which is far more MFMA-efficient than T small ones.
 //
+// The policy step (normalise, MLP chain, keyed sample, log-prob, row store) is csrc/policy_step.h
+// and the env physics csrc/env_core.h, both shared with csrc/eval.hip (and act.hip); this file
+// keeps what is the rollout's own: the moments, the x^T groups, the [T][E] buffer stores, the
+// episode bookkeeping and the per-step normalisation hand-offs.
+//
 // Reference: train.py:82-106 (one env, batch 1, python loop) and model.py:68-80.
-#include <type_traits>
-
-#include "kernels.h"
-#include "mlp_core.h"
+#include "env_core.h"
+#include "policy_step.h"
 
 namespace {
-
-constexpr float LOG_2PI_F = 1.8378770664093453f;
-constexpr float SYN_DECAY = 0.9f, SYN_DRIVE = 0.1f, SYN_NOISE = 0.05f, SYN_RESET = 0.1f;
-constexpr float SYN_TERM_P = 0.002f;
-
-// observation of env r, dim d.  KIND is a template parameter: with a runtime kind the
-// pendulum's libm cosf/sinf (Payne-Hanek reduction, divergent per lane) was inlined into each
-// of the ROWS unrolled iterations of the synthetic env's observe loop (~2,500 dead
-// instructions per step and a 3x slower phase).
-template <int KIND>
-DEV float env_obs(const float* st, int S, int r, int d) {
-  if constexpr (KIND == 1) {  // pendulum: (cos th, sin th, thdot)
-    const float th = st[r * S + 0];
-    return d == 0 ? cosf(th) : (d == 1 ? sinf(th) : st[r * S + 1]);
-  } else {
-    return st[r * S + d];
-  }
-}
 
 // ---- per-step observation normalisation inside the launch (RolloutArgs sn_*) ----
 // 8-byte {tag, fp32 bits} granules, stored and loaded relaxed at agent scope (sc1 vector accesses:
@@ -176,6 +161,40 @@ DEV bool sn_gather(const RolloutArgs& a, int step, int tid, float* nm, float* ni
   return true;
 }
 
+// The launch's dynamic LDS: the kernel's pointers and the host's byte count (null smem: measuring)
+// come from this one carve.  SN: the per-step normalisation's extra pieces.
+template <int DT, int ROWS, bool SN>
+struct RolloutLds {
+  using XB = typename Prec<XStore<DT>::DTX>::T;   // buffer precision (bf16 when DT is fp8)
+  LdsCarve cv;
+  const int O, A, S;
+  float* st = cv.take<float>(ROWS * S);           // env state
+  PolicyTiles<DT> t;
+  float* act = cv.take<float>(ROWS * A);          // the step's actions and their noise
+  float* epsb = cv.take<float>(ROWS * A);
+  float* s1 = cv.take<float>(O);                  // the launch's moments about the shift
+  float* s2 = cv.take<float>(O);
+  float* done_s = cv.take<float>(ROWS);
+  int* eplen = cv.take<int>(ROWS);
+  float* epret = cv.take<float>(ROWS);
+  float* epacc = cv.take<float>(2 * ROWS);
+  uint32_t* kes = cv.take<uint32_t>(3 * ROWS);    // per-env key prefixes of this step: action, env, reset
+  float* wdrv = cv.take<float>(S);                // synthetic dynamics tables (env_core.h syn_tables)
+  int* jdx = cv.take<int>(S);
+  float* lsg = cv.take<float>(2 * A);             // [log sigma | sigma]
+  // SN: the iteration shift and this step's (mean, 1/std) of every feature; the timeout flag;
+  // the reduce's per-wave partials
+  float* shs = SN ? cv.take<float>(O) : nullptr;
+  float* nm = SN ? cv.take<float>(O) : nullptr;
+  float* ninv = SN ? cv.take<float>(O) : nullptr;
+  int* sn_fail = SN ? cv.take<int>(1) : nullptr;
+  double* sn_red = SN ? cv.take<double>(32) : nullptr;
+  XB* xsb;   // fp8: bf16 staging tile of the buffer rows (policy_step.h store_tile_rows)
+  __host__ __device__ RolloutLds(char* smem, const RolloutArgs& a)
+      : cv(smem), O(a.O), A(a.A), S(a.S), t(cv, a.net, ROWS, a.A),
+        xsb(DT == DT_FP8 ? cv.take<XB>(ROWS * a.net.d1) : nullptr) {}
+};
+
 // NW waves per workgroup: a 16-env tile is one workgroup per CU at E = 4096, so the 8-wave
 // form (2 waves per SIMD) doubles the threads of the VALU-heavy observe / sample / env phases
 // and gives the SIMDs a second wave to hide latency with; the MFMA layers use the first waves.
@@ -190,82 +209,34 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e0 = blockIdx.x * ROWS;
   const int nvalid = min(ROWS, a.E - e0);
-  const int O = a.O, A = a.A, S = a.S;
-  const int ld1 = Lds<DT>::stride(a.d1), ld2 = Lds<DT>::stride(a.d2), ld3 = Lds<DT>::stride(a.d3);
+  const int O = a.O, A = a.A, S = a.S, d1 = a.net.d1;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  LdsCarve cv(smem);
-  float* st = cv.take<float>(ROWS * S);
-  T* xs = cv.take<T>(ROWS * ld1);
-  T* h1 = cv.take<T>(ROWS * ld2);
-  T* h2 = cv.take<T>(ROWS * ld3);
-  float* mu = cv.take<float>(ROWS * A);
-  float* act = cv.take<float>(ROWS * A);
-  float* epsb = cv.take<float>(ROWS * A);
-  float* s1 = cv.take<float>(O);
-  float* s2 = cv.take<float>(O);
-  float* done_s = cv.take<float>(ROWS);
-  int* eplen = cv.take<int>(ROWS);
-  float* epret = cv.take<float>(ROWS);
-  float* epacc = cv.take<float>(2 * ROWS);
-  uint32_t* kes = cv.take<uint32_t>(3 * ROWS);   // per-env key prefixes of this step: action, env, reset
-  float* wdrv = cv.take<float>(S);                // synthetic dynamics: drive weight of state dim d
-  int* jdx = cv.take<int>(S);                     //                     action index driving dim d
-  float* lsg = cv.take<float>(2 * A);             // per action dim: log sigma [0, A), sigma [A, 2A)
-  // SN: the iteration shift and this step's (mean, 1/std) of every feature; the timeout flag
-  float* shs = SN ? cv.take<float>(O) : nullptr;
-  float* nm = SN ? cv.take<float>(O) : nullptr;
-  float* ninv = SN ? cv.take<float>(O) : nullptr;
-  int* sn_fail = SN ? cv.take<int>(1) : nullptr;
-  double* sn_red = SN ? cv.take<double>(32) : nullptr;   // the reduce's per-wave partials
-  // fp8: the MFMA tile is e4m3 but the buffer rows are bf16 — a bf16 staging tile lets them
-  // leave as 16-byte row chunks (element stores strided by the row length were 2.6x the bf16
-  // kernel's time)
-  using XB = typename Prec<XStore<DT>::DTX>::T;
+  const RolloutLds<DT, ROWS, SN> L(smem, a);
+  PolicyStep<DT, ROWS, NW> ps(a.net, L.t);
+  const int ld1 = L.t.ld1;
+  using PX = Prec<XStore<DT>::DTX>;
   constexpr bool STAGE = DT == DT_FP8;
-  XB* xsb = STAGE ? cv.take<XB>(ROWS * a.d1) : nullptr;
-
-  const T* W = reinterpret_cast<const T*>(a.W);
-  const T* W1 = W + a.off_w1;
-  const T* W2 = W + a.off_w2;
-  const T* W3 = W + a.off_w3;
-  using PX = Prec<XStore<DT>::DTX>;              // buffer precision (bf16 when DT is fp8)
   typename PX::T* xo = reinterpret_cast<typename PX::T*>(a.x_out);
-  // per-layer dequant scales: device array (fp8 images, refreshed on-device) or kernel args
-  const float sc1 = a.qscale ? a.qscale[0] : a.s1;
-  const float sc2 = a.qscale ? a.qscale[1] : a.s2;
-  const float sc3 = a.qscale ? a.qscale[2] : a.s3;
 
   // ---- load state, zero the padded activation tiles (pad columns stay constant) ----
   for (int i = tid; i < ROWS * S; i += NTHR) {
     int r = i / S, d = i - r * S;
-    st[i] = (r < nvalid) ? a.state[(size_t)(e0 + r) * S + d] : 0.f;
+    L.st[i] = (r < nvalid) ? a.state[(size_t)(e0 + r) * S + d] : 0.f;
   }
-  preset_pad<DT>(h1, ld2, ROWS, a.n1, tid, NTHR);   // the layers' epilogues write columns < n
-  preset_pad<DT>(h2, ld3, ROWS, a.n2, tid, NTHR);
-  for (int d = tid; d < O; d += NTHR) { s1[d] = 0.f; s2[d] = 0.f; }
+  for (int d = tid; d < O; d += NTHR) { L.s1[d] = 0.f; L.s2[d] = 0.f; }
   if constexpr (SN) {
-    for (int d = tid; d < O; d += NTHR) shs[d] = a.shift[d];
-    if (tid == 0) *sn_fail = 0;
+    for (int d = tid; d < O; d += NTHR) L.shs[d] = a.shift[d];
+    if (tid == 0) *L.sn_fail = 0;
   }
-  for (int d = tid; d < S; d += NTHR) {   // per-dim constants once per launch (no per-step modulo)
-    wdrv[d] = 0.5f + (float)(d % 7) / 7.0f;
-    jdx[d] = d % A;
-  }
-  // log_std is fixed during a rollout: log sigma and sigma once per launch, not a global load
-  // (and an exp) per sampled dim and step
-  for (int j = tid; j < A; j += NTHR) {
-    const float ls = a.log_std[j];
-    const float lsig = a.std_var ? 0.5f * ls : ls;
-    lsg[j] = lsig;
-    lsg[A + j] = __expf(lsig);
-  }
+  syn_tables(L.wdrv, L.jdx, S, A, tid, NTHR);
+  ps.setup(L.lsg, tid);
   if (tid < ROWS) {
     int e = e0 + tid;
-    eplen[tid] = (tid < nvalid) ? a.ep_len[e] : 0;
-    epret[tid] = (tid < nvalid) ? a.ep_ret[e] : 0.f;
-    epacc[2 * tid] = 0.f;
-    epacc[2 * tid + 1] = 0.f;
+    L.eplen[tid] = (tid < nvalid) ? a.ep_len[e] : 0;
+    L.epret[tid] = (tid < nvalid) ? a.ep_ret[e] : 0.f;
+    L.epacc[2 * tid] = 0.f;
+    L.epacc[2 * tid + 1] = 0.f;
   }
   __syncthreads();
 
@@ -273,10 +244,9 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
   // loaded once instead of once per step (the compiler cannot hoist them past the stores)
   float hm = 0.f, his = 1.f, hsh = 0.f;
   if (tid < O) { hm = a.mean[tid]; his = a.inv_std[tid]; hsh = a.shift[tid]; }
-  BPre<DT, ROWS / 16> pf;   // cross-barrier weight prefetch of each layer's first k-chunk
-  // bf16 / fp32: the LDS tile and the buffer share the element type (fp8 tiles feed a bf16 buffer)
-  // (split-bf16: the LDS tile and the buffer share the 32-byte hi|lo group layout too)
   constexpr bool SPLIT = IsSplit<DT>::value;
+  // the buffer rows leave from the LDS tile (store_tile_rows) unless the tile's element type is
+  // not the buffer's
   constexpr bool XO_FROM_LDS = std::is_same_v<T, typename PX::T> || SPLIT || STAGE;
   // the observe loop keeps this feature's ROWS values in the buffer type, or as fp32 for split
   // storage (split once, at the 32-byte x^T group store)
@@ -307,10 +277,10 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
     // ---- (a) observe, moments, normalise -> LDS tile + global buffer row ----
     auto observe = [&](auto kind_tag) {
       constexpr int KIND = decltype(kind_tag)::value;
-      for (int d = tid; d < a.d1; d += NTHR) {
+      for (int d = tid; d < d1; d += NTHR) {
         float m = hm, is = his, sh = hsh;
         if constexpr (SN) {
-          if (d < O) { m = nm[d]; is = ninv[d]; }
+          if (d < O) { m = L.nm[d]; is = L.ninv[d]; }
         } else {
           if (d != tid && d < O) { m = a.mean[d]; is = a.inv_std[d]; sh = a.shift[d]; }
         }
@@ -320,18 +290,18 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
         for (int r = 0; r < ROWS; ++r) {
           float xv;
           if (d < O) {
-            float o = env_obs<KIND>(st, S, r, d);
+            float o = env_obs<KIND>(L.st, S, r, d);
             if (!SN && !last && r < nvalid) { float dd = o - sh; ls1 += dd; ls2 += dd * dd; }
-            xv = fminf(fmaxf((o - m) * is, -5.f), 5.f);
+            xv = norm_clamp(o, m, is);
           } else {
-            xv = (d == O) ? 1.f : 0.f;
+            xv = pad_col(d, O);
           }
-          P::put(xs, r * ld1 + d, xv);
+          P::put(L.t.xs, r * ld1 + d, xv);
           if constexpr (SPLIT) grp[r] = xv;
           else grp[r] = PX::cvt(xv);
-          if constexpr (STAGE) xsb[r * a.d1 + d] = grp[r];
+          if constexpr (STAGE) L.xsb[r * d1 + d] = grp[r];
         }
-        if (!SN && d < O) { s1[d] += ls1; s2[d] += ls2; }
+        if (!SN && d < O) { L.s1[d] += ls1; L.s2[d] += ls2; }
         // full-batch update operand: rows m = tb*E + e0 + r are contiguous 8-groups of the FM
         // layout (host guarantees E % 16 == 0), written once per rollout instead of per epoch
         if (a.xT_out != nullptr && !last) {
@@ -371,19 +341,19 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
         auto moments = [&](auto kind_tag) {
           constexpr int KIND = decltype(kind_tag)::value;
           for (int d = tid; d < O; d += NTHR) {
-            const float sh = shs[d];
+            const float sh = L.shs[d];
             float ls1 = 0.f, ls2 = 0.f;
             // every row read unconditionally (st holds ROWS rows), the invalid ones masked: a
             // per-row branch kept the compiler from batching the LDS reads (one round trip each)
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
-              const float o = env_obs<KIND>(st, S, r, d);
+              const float o = env_obs<KIND>(L.st, S, r, d);
               const float dd = r < nvalid ? o - sh : 0.f;
               ls1 += dd;
               ls2 += dd * dd;
             }
-            s1[d] += ls1;
-            s2[d] += ls2;
+            L.s1[d] += ls1;
+            L.s2[d] += ls2;
             sn_put(a.sn_g1 + sn_g1_index(0, d, (int)blockIdx.x, O, (int)gridDim.x), tag, ls1);
             sn_put(a.sn_g1 + sn_g1_index(1, d, (int)blockIdx.x, O, (int)gridDim.x), tag, ls2);
           }
@@ -397,92 +367,50 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
           pm2 = a.sn_m2[dfirst];
         }
         PH_ABS(11);
-        if (a.kind == 1) moments(std::integral_constant<int, 1>{});
-        else moments(std::integral_constant<int, 0>{});
+        env_kind_switch(a.kind, moments);
         PH(7);
         PH_ABS(12);
         unsigned npr = 0, npg = 0;
-        if (!sn_reduce<NW>(a, (int)gridDim.x, step, wave, lane, shs, sn_red, pmean, pm2, npr) && lane == 0)
-          *sn_fail = 1;
+        if (!sn_reduce<NW>(a, (int)gridDim.x, step, wave, lane, L.shs, L.sn_red, pmean, pm2, npr) && lane == 0)
+          *L.sn_fail = 1;
         PH(8);
         PH_ABS(13);
         // the gather polls start once this workgroup's reducers are done: polling from the
         // other waves during the reduce queued ahead of the reducers' own loads on the CU
         __syncthreads();
-        if (!sn_gather<NTHR>(a, step, tid, nm, ninv, npg) && lane == 0) *sn_fail = 1;
+        if (!sn_gather<NTHR>(a, step, tid, L.nm, L.ninv, npg) && lane == 0) *L.sn_fail = 1;
         PH(9);
         PH_ABS(14);
         if (a.tstamp != nullptr && step == 8) ph_acc[15] = ((unsigned long long)npg << 32) | npr;
         __syncthreads();
         PH(10);
-        if (*sn_fail) {   // a peer never published: give up (the host raises)
+        if (*L.sn_fail) {   // a peer never published: give up (the host raises)
           if (tid == 0) __hip_atomic_store(a.sn_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           return;
         }
       }
     }
-    if (a.kind == 1) observe(std::integral_constant<int, 1>{});
-    else observe(std::integral_constant<int, 0>{});
-    if (!last) layer_prefetch<DT, ROWS, NW>(pf, W1, a.d1, a.n1, wave, lane);
+    env_kind_switch(a.kind, observe);
+    if (!last) ps.prefetch(wave, lane);
     __syncthreads();
-    if constexpr (XO_FROM_LDS) {
-      // row-major buffer rows from the normalised LDS tile: one 16-byte store per 16 bytes of
-      // features instead of ROWS element stores per feature (fire-and-forget, overlaps the MFMA
-      // layers)
-      constexpr int EPC = 16 / sizeof(XB);
-      const int ch = a.d1 / EPC;
-      for (int i = tid; i < nvalid * ch; i += NTHR) {
-        const int r = i / ch, c = i - r * ch;
-        const void* src = STAGE ? static_cast<const void*>(xsb + r * a.d1 + c * EPC)
-                                : static_cast<const void*>(xs + r * ld1 + c * EPC);
-        *reinterpret_cast<uint4*>(xo + ((size_t)tb * a.buf_E + e0 + r) * a.d1 + c * EPC) =
-            *reinterpret_cast<const uint4*>(src);
-      }
-    }
+    if constexpr (XO_FROM_LDS)
+      store_tile_rows<DT, NTHR>(xo + ((size_t)tb * a.buf_E + e0) * d1, L.t, L.xsb, d1, nvalid, tid);
     if (last) break;
-    // (env, step) key prefixes of the sample / env phases, shared by every dim of the step:
-    // hashed by the last wave's lanes (idle in the narrow policy layers) before fc1, so the
-    // layers' barriers publish them and the sample phase needs no barrier of its own (the
-    // previous step's env phase, their last reader, ended in a barrier)
+    // the key prefixes of the sample / env phases: hashed before fc1, so the layers' barriers
+    // publish them and the sample phase needs no barrier of its own (the previous step's env
+    // phase, their last reader, ended in a barrier)
     const uint32_t kstep = a.t0 + (uint32_t)step;
-    if (tid >= NTHR - ROWS) {
-      const int r = tid - (NTHR - ROWS);
-      const uint32_t e = (uint32_t)(e0 + r);
-      kes[r] = key_es(a.key_action, e, kstep);
-      kes[ROWS + r] = key_es(a.key_env, e, kstep);
-      kes[2 * ROWS + r] = key_es(a.key_reset, e, kstep);
-    }
+    key_prefixes<ROWS, NTHR>(L.kes, {a.key_action, a.key_env, a.key_reset}, (uint32_t)e0, kstep, tid);
     PH(0);   // (a) observe -> after its barrier
-    // ---- (b) policy MLP ----
-    layer_gemm<DT, ROWS, NW, EPI_TANH, true>(xs, ld1, a.d1, W1, a.n1, h1, ld2, sc1, wave, lane, nullptr, 0, 0, 0, &pf);
-    layer_prefetch<DT, ROWS, NW>(pf, W2, a.d2, a.n2, wave, lane);
-    __syncthreads();
-    PH(1);
-    layer_gemm<DT, ROWS, NW, EPI_TANH, true>(h1, ld2, a.d2, W2, a.n2, h2, ld3, sc2, wave, lane, nullptr, 0, 0, 0, &pf);
-    layer_prefetch<DT, ROWS, NW>(pf, W3, a.d3, a.n3, wave, lane);
-    __syncthreads();
-    PH(2);
-    layer_gemm<DT, ROWS, NW, EPI_LINEAR_F32, true>(h2, ld3, a.d3, W3, a.n3, mu, A, sc3, wave, lane, nullptr, 0, 0, 0,
-                                                   &pf);
-    __syncthreads();
-    PH(3);   // fc1, fc2, fc3 (each incl. barrier)
-    // ---- (c) sample a = mu + sigma * eps (one Box-Muller pair -> two action dims) ----
-    const int npa = (A + 1) >> 1;
-    for (int i = tid; i < ROWS * npa; i += NTHR) {
-      const int r = i / npa, q = i - r * npa;
-      const float2 g = gauss_pair(kes[r], (uint32_t)q);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int j = 2 * q + h;
-        if (j < A) {
-          const float eps = h ? g.y : g.x;
-          const float av = mu[r * A + j] + lsg[A + j] * eps;
-          act[r * A + j] = av;
-          epsb[r * A + j] = eps;
-          if (r < nvalid) a.actions[((size_t)tb * a.buf_E + e0 + r) * A + j] = av;
-        }
-      }
-    }
+    // ---- (b) policy MLP: PH(1..3) = fc1, fc2, fc3 (each incl. barrier) ----
+    ps.layers(wave, lane, [&](auto l) { PH(decltype(l)::value); });
+    // ---- (c) sample a = mu + sigma * eps ----
+    sample_loop<ROWS, NTHR>(L.kes, A, tid, true, [&](int r, int j, float eps) {
+      const float av = L.t.mu[r * A + j] + L.lsg[A + j] * eps;
+      L.act[r * A + j] = av;
+      L.epsb[r * A + j] = eps;
+      if (r < nvalid) a.actions[((size_t)tb * a.buf_E + e0 + r) * A + j] = av;
+    });
     __syncthreads();
     PH(4);   // (c) sample
     // ---- (d) per-env: logp, reward, termination, episode bookkeeping ----
@@ -494,13 +422,8 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
       float lp = 0.f, err = 0.f;
       const int na = min(A, O);
       for (int j = l; j < A; j += LPE) {
-        const float ep = epsb[r * A + j];
-        lp += -0.5f * ep * ep - lsg[j];
-        if (a.kind != 1 && j < na) {
-          const float ac = fminf(fmaxf(act[r * A + j], -1.f), 1.f);
-          const float d = ac - fast_tanh(st[r * S + j]);
-          err += d * d;
-        }
+        lp += logp_term(L.epsb[r * A + j], L.lsg[j]);
+        if (a.kind != 1 && j < na) err += syn_err_term(L.act[r * A + j], L.st[r * S + j]);
       }
 #pragma unroll
       for (int o = LPE / 2; o > 0; o >>= 1) {
@@ -508,31 +431,20 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
         err += __shfl_xor(err, o, LPE);
       }
       if (l == 0) {
-        lp -= 0.5f * LOG_2PI_F * (float)A;
-        float rew;
-        bool term = false;
-        if (a.kind == 1) {
-          float th = st[r * S], thd = st[r * S + 1];
-          float u = fminf(fmaxf(act[r * A], -2.f), 2.f);
-          float thn = fmodf(th + 3.14159265358979f, 6.28318530717959f);
-          if (thn < 0.f) thn += 6.28318530717959f;
-          thn -= 3.14159265358979f;
-          rew = -(thn * thn + 0.1f * thd * thd + 0.001f * u * u);
-        } else {
-          rew = 1.f - err / (float)na;
-          term = uniform01(keyed(a.key_term, (uint32_t)e, kstep, 0u)) < SYN_TERM_P;
-        }
-        int el = eplen[r] + 1;
-        float er_ = epret[r] + rew;
+        lp -= logp_const(A);
+        bool term;
+        const float rew = env_reward(a.kind, L.st, S, L.act, A, r, err, na, a.key_term, (uint32_t)e, kstep, term);
+        int el = L.eplen[r] + 1;
+        float er_ = L.epret[r] + rew;
         bool done = term || (el >= a.limit);
         if (done) {
-          if (r < nvalid) { epacc[2 * r] += er_; epacc[2 * r + 1] += 1.f; }
+          if (r < nvalid) { L.epacc[2 * r] += er_; L.epacc[2 * r + 1] += 1.f; }
           el = 0;
           er_ = 0.f;
         }
-        eplen[r] = el;
-        epret[r] = er_;
-        done_s[r] = done ? 1.f : 0.f;
+        L.eplen[r] = el;
+        L.epret[r] = er_;
+        L.done_s[r] = done ? 1.f : 0.f;
         if (r < nvalid) {
           size_t o = (size_t)tb * a.buf_E + e;
           float rc = rew;
@@ -546,82 +458,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
     __syncthreads();
     PH(5);   // (d) logp / reward
     // ---- (e) state transition (+ in-place reset on done) ----
-    if (a.kind == 1) {
-      if (tid < ROWS) {
-        const int r = tid, e = e0 + r;
-        if (done_s[r] > 0.5f) {
-          float u0 = uniform01(keyed(a.key_reset, (uint32_t)e, kstep, 0u));
-          float u1 = uniform01(keyed(a.key_reset, (uint32_t)e, kstep, 1u));
-          st[r * S] = (2.f * u0 - 1.f) * 3.14159265358979f;
-          st[r * S + 1] = 2.f * u1 - 1.f;
-        } else {
-          float th = st[r * S], thd = st[r * S + 1];
-          float u = fminf(fmaxf(act[r * A], -2.f), 2.f);
-          float nthd = thd + (-3.f * 10.f / 2.f * sinf(th + 3.14159265358979f) + 3.f * u) * 0.05f;
-          float nth = th + nthd * 0.05f;
-          nthd = fminf(fmaxf(nthd, -8.f), 8.f);
-          st[r * S] = nth;
-          st[r * S + 1] = nthd;
-        }
-      }
-    } else {
-      // item = (row r, dim pair p), consecutive threads on consecutive pairs of one row: the
-      // 16 x S/2 items spread evenly over the threads (one Box-Muller pair per item) and the
-      // per-dim constants come from LDS tables filled once per launch.  Two items per turn with
-      // every LDS read of both issued before any state store (items never share a state slot),
-      // so the second item's loads, hashes and transcendentals overlap the first's instead of
-      // waiting behind its stores; the reset / step choice is a select, not a branch.
-      const int np = (S + 1) >> 1;
-      int r = tid / np, p = tid - r * np;
-      const int sr = NTHR / np, sp = NTHR - sr * np;
-      struct In { float st0, st1, a0, a1, w0, w1; uint32_t key; bool done, has1; int d0; };
-      auto load = [&](int rr, int pp) {
-        In q;
-        q.d0 = 2 * pp;
-        q.has1 = q.d0 + 1 < S;
-        const int d1 = q.has1 ? q.d0 + 1 : q.d0;
-        q.done = done_s[rr] > 0.5f;
-        q.key = q.done ? kes[2 * ROWS + rr] : kes[ROWS + rr];
-        q.st0 = st[rr * S + q.d0];
-        q.st1 = st[rr * S + d1];
-        q.a0 = act[rr * A + jdx[q.d0]];
-        q.a1 = act[rr * A + jdx[d1]];
-        q.w0 = wdrv[q.d0];
-        q.w1 = wdrv[d1];
-        return q;
-      };
-      auto step_item = [&](const In& q, int pp, float& n0, float& n1) {
-        const float2 g = gauss_pair(q.key, (uint32_t)pp);
-        if (q.done) {
-          n0 = SYN_RESET * g.x;
-          n1 = SYN_RESET * g.y;
-        } else {
-          const float a0 = fminf(fmaxf(q.a0, -1.f), 1.f);
-          const float a1 = fminf(fmaxf(q.a1, -1.f), 1.f);
-          n0 = SYN_DECAY * q.st0 + SYN_DRIVE * fast_tanh(q.w0 * a0) + SYN_NOISE * g.x;
-          n1 = SYN_DECAY * q.st1 + SYN_DRIVE * fast_tanh(q.w1 * a1) + SYN_NOISE * g.y;
-        }
-      };
-      while (r < ROWS) {
-        int r2 = r + sr, p2 = p + sp;
-        if (p2 >= np) { p2 -= np; ++r2; }
-        const bool v2 = r2 < ROWS;
-        const In q1 = load(r, p);
-        const In q2 = load(v2 ? r2 : r, v2 ? p2 : p);   // past the end: re-read item 1 (unused)
-        float n10, n11, n20, n21;
-        step_item(q1, p, n10, n11);
-        step_item(q2, v2 ? p2 : p, n20, n21);
-        st[r * S + q1.d0] = n10;
-        if (q1.has1) st[r * S + q1.d0 + 1] = n11;
-        if (v2) {
-          st[r2 * S + q2.d0] = n20;
-          if (q2.has1) st[r2 * S + q2.d0 + 1] = n21;
-        }
-        r = r2 + sr;
-        p = p2 + sp;
-        if (p >= np) { p -= np; ++r; }
-      }
-    }
+    env_transition<ROWS, NTHR>(a.kind, L.st, S, L.act, A, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
     __syncthreads();
     PH(6);   // (e) env transition
   }
@@ -633,105 +470,87 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
 #undef PH
 #undef PH_ABS
   // ---- write back env state, episode trackers, partial moments / episode stats ----
-  for (int i = tid; i < nvalid * S; i += NTHR) a.state[(size_t)e0 * S + i] = st[i];
+  for (int i = tid; i < nvalid * S; i += NTHR) a.state[(size_t)e0 * S + i] = L.st[i];
   if (tid < nvalid) {
-    a.ep_len[e0 + tid] = eplen[tid];
-    a.ep_ret[e0 + tid] = epret[tid];
+    a.ep_len[e0 + tid] = L.eplen[tid];
+    a.ep_ret[e0 + tid] = L.epret[tid];
   }
   float* mom = a.mom + (size_t)blockIdx.x * 2 * O;
-  for (int d = tid; d < O; d += NTHR) { mom[d] = s1[d]; mom[O + d] = s2[d]; }
+  for (int d = tid; d < O; d += NTHR) { mom[d] = L.s1[d]; mom[O + d] = L.s2[d]; }
   if (tid == 0) {
     float sr = 0.f, sc = 0.f;
-    for (int r = 0; r < ROWS; ++r) { sr += epacc[2 * r]; sc += epacc[2 * r + 1]; }
+    for (int r = 0; r < ROWS; ++r) { sr += L.epacc[2 * r]; sc += L.epacc[2 * r + 1]; }
     a.epstat[2 * blockIdx.x] = sr;
     a.epstat[2 * blockIdx.x + 1] = sc;
   }
 }
 
-template <int DT, int ROWS>
-size_t rollout_lds(const RolloutArgs& a) {
-  auto al = [](size_t b) { return (b + 15) & ~size_t(15); };
-  using T = typename Prec<DT>::T;
-  size_t b = 0;
-  b += al(sizeof(float) * ROWS * a.S);
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d1));
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d2));
-  b += al(sizeof(T) * ROWS * Lds<DT>::stride(a.d3));
-  b += 3 * al(sizeof(float) * ROWS * a.A);
-  b += 2 * al(sizeof(float) * a.O);
-  b += al(sizeof(float) * ROWS) + al(sizeof(int) * ROWS) + al(sizeof(float) * ROWS) + al(sizeof(float) * 2 * ROWS);
-  b += al(sizeof(uint32_t) * 3 * ROWS);
-  b += al(sizeof(float) * a.S) + al(sizeof(int) * a.S);
-  b += al(sizeof(float) * 2 * a.A);
-  if (a.sn_g1 != nullptr) b += 3 * al(sizeof(float) * a.O) + al(sizeof(int)) + al(sizeof(double) * 32);
-  if (DT == DT_FP8) b += al(sizeof(__bf16) * ROWS * a.d1);   // bf16 staging tile of the buffer rows
-  return b;
-}
-
 int g_rollout_waves = 8;   // 4 or 8 (set_rollout_waves: A/B diagnostics)
 
+// f(DT, ROWS, NW as integral_constants) for the form a launch takes.  16-row bf16x3 / bf16 / fp8
+// tiles run 8 waves unless set_rollout_waves(4); the other forms exist with 4 waves only.
+template <typename F>
+auto dispatch_form(int dt, int rows, F&& f) {
+  return dispatch_dt(dt, [&](auto d) {
+    auto go = [&](auto r) {
+      using W4 = std::integral_constant<int, 4>;
+      if constexpr (POLICY_WAVES<decltype(d)::value, decltype(r)::value> == 8) {
+        if (g_rollout_waves != 4) return f(d, r, std::integral_constant<int, 8>{});
+      }
+      return f(d, r, W4{});
+    };
+    return rows == 32 ? go(std::integral_constant<int, 32>{}) : go(std::integral_constant<int, 16>{});
+  });
+}
+
+// the launch's dynamic-LDS bytes (and the kernel's attribute for them)
+template <int DT, int ROWS, int NW, bool SN>
+size_t launch_lds(const RolloutArgs& a) {
+  const size_t lds = RolloutLds<DT, ROWS, SN>(nullptr, a).cv.off;
+  if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, SN>>(lds);
+  return lds;
+}
+
+// Per-step normalisation: every workgroup must be resident at once (the hand-offs wait on all
+// of them), so the launch is cooperative (the runtime refuses a grid that cannot be co-resident)
+// and its grid is also kept one workgroup per CU below the occupancy answer (MI355X_MICROARCH.md:
+// the API can overstate residency by one per CU).  cap: the largest grid the launch accepts
+// (0: none; the gather holds 2 O granules in registers).
 template <int DT, int ROWS, int NW>
-void launch_nw(const RolloutArgs& a, hipStream_t s) {
-  const size_t lds = rollout_lds<DT, ROWS>(a);
+hipError_t stepnorm_cap(const RolloutArgs& a, size_t lds, int& cap) {
+  int per_cu = 0, dev = 0, ncu = 0;
+  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true>), NW * 64, lds);
+  if (e == hipSuccess) e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  cap = ncu * (per_cu > 1 ? per_cu - 1 : per_cu);
+  if (cap > SN_MAX_BLOCKS) cap = SN_MAX_BLOCKS;
+  if (e != hipSuccess || a.O > SN_MAX_O) cap = 0;
+  return e;
+}
+
+template <int DT, int ROWS, int NW>
+void launch(const RolloutArgs& a, hipStream_t s) {
   const int nblk = (a.E + ROWS - 1) / ROWS;
   if (a.sn_g1 == nullptr) {
-    if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, false>>(lds);
+    const size_t lds = launch_lds<DT, ROWS, NW, false>(a);
     hipLaunchKernelGGL((rollout_kernel<DT, ROWS, NW, false>), dim3(nblk), dim3(NW * 64), lds, s, a);
     HIP_CHECK_LAUNCH();
     return;
   }
-  // per-step normalisation: every workgroup must be resident at once (the hand-offs wait on all
-  // of them).  Cooperative launch: the runtime refuses a grid that cannot be co-resident; the
-  // grid is also kept one workgroup per CU below the occupancy answer (MI355X_MICROARCH.md:
-  // the API can overstate residency by one per CU)
-  auto kfn = rollout_kernel<DT, ROWS, NW, true>;
-  if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, true>>(lds);
-  int per_cu = 0, dev = 0, ncu = 0;
-  hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kfn), NW * 64, lds);
-  if (e == hipSuccess) e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const size_t lds = launch_lds<DT, ROWS, NW, true>(a);
+  int cap = 0;
+  hipError_t e = stepnorm_cap<DT, ROWS, NW>(a, lds, cap);
+  if (e == hipSuccess && nblk > cap) e = hipErrorCooperativeLaunchTooLarge;
   if (e != hipSuccess) {
     dppo_note_error(e, __FILE__, __LINE__);
     return;
   }
-  const int cap = ncu * (per_cu > 1 ? per_cu - 1 : per_cu);
-  if (nblk > cap || nblk > SN_MAX_BLOCKS || a.O > SN_MAX_O) {
-    dppo_note_error(hipErrorCooperativeLaunchTooLarge, __FILE__, __LINE__);
-    return;
-  }
   RolloutArgs aa = a;
   void* args[] = {&aa};
-  e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(kfn), dim3(nblk), dim3(NW * 64), args, (unsigned)lds, s);
+  e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true>), dim3(nblk),
+                                 dim3(NW * 64), args, (unsigned)lds, s);
   if (e != hipSuccess) dppo_note_error(e, __FILE__, __LINE__);
-}
-
-// the largest grid the per-step normalisation launch accepts (0: none)
-template <int DT, int ROWS, int NW>
-int stepnorm_cap(const RolloutArgs& a) {
-  const size_t lds = rollout_lds<DT, ROWS>(a);
-  auto kfn = rollout_kernel<DT, ROWS, NW, true>;
-  if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, true>>(lds);
-  int per_cu = 0, dev = 0, ncu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kfn), NW * 64, lds) !=
-          hipSuccess ||
-      hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  if (a.O > SN_MAX_O) return 0;   // the gather holds 2 O granules in registers
-  const int cap = ncu * (per_cu > 1 ? per_cu - 1 : per_cu);
-  return cap < SN_MAX_BLOCKS ? cap : SN_MAX_BLOCKS;
-}
-
-template <int DT, int ROWS>
-void launch_t(const RolloutArgs& a, hipStream_t s) {
-  // fp32 operands and 32-env tiles: the 8-wave form spills (twice the fragment registers)
-  if (g_rollout_waves == 4 || DT == DT_F32 || ROWS > 16) launch_nw<DT, ROWS, 4>(a, s);
-  else launch_nw<DT, ROWS, 8>(a, s);
-}
-template <int DT, int ROWS>
-int cap_t(const RolloutArgs& a) {
-  if (g_rollout_waves == 4 || DT == DT_F32 || ROWS > 16) return stepnorm_cap<DT, ROWS, 4>(a);
-  return stepnorm_cap<DT, ROWS, 8>(a);
 }
 
 }  // namespace
@@ -740,28 +559,16 @@ extern "C" void set_rollout_waves(int nw) { g_rollout_waves = nw; }
 
 // workgroups the per-step normalisation launch can hold co-resident (its grid must not exceed it)
 extern "C" int rollout_stepnorm_cap(int dt, const RolloutArgs& a, int rows) {
-  if (rows == 32) {
-    if (dt == DT_F32) return cap_t<DT_F32, 32>(a);
-    if (dt == DT_BF16) return cap_t<DT_BF16, 32>(a);
-    if (dt == DT_S3) return cap_t<DT_S3, 32>(a);
-    return cap_t<DT_FP8, 32>(a);
-  }
-  if (dt == DT_F32) return cap_t<DT_F32, 16>(a);
-  if (dt == DT_BF16) return cap_t<DT_BF16, 16>(a);
-  if (dt == DT_S3) return cap_t<DT_S3, 16>(a);
-  return cap_t<DT_FP8, 16>(a);
+  return dispatch_form(dt, rows, [&](auto d, auto r, auto w) {
+    constexpr int DT = decltype(d)::value, ROWS = decltype(r)::value, NW = decltype(w)::value;
+    int cap = 0;
+    (void)stepnorm_cap<DT, ROWS, NW>(a, launch_lds<DT, ROWS, NW, true>(a), cap);   // a failed query: cap 0
+    return cap;
+  });
 }
 
 extern "C" void launch_rollout(int dt, const RolloutArgs& a, int rows, hipStream_t s) {
-  if (rows == 32) {
-    if (dt == DT_F32) launch_t<DT_F32, 32>(a, s);
-    else if (dt == DT_BF16) launch_t<DT_BF16, 32>(a, s);
-    else if (dt == DT_S3) launch_t<DT_S3, 32>(a, s);
-    else launch_t<DT_FP8, 32>(a, s);
-  } else {
-    if (dt == DT_F32) launch_t<DT_F32, 16>(a, s);
-    else if (dt == DT_BF16) launch_t<DT_BF16, 16>(a, s);
-    else if (dt == DT_S3) launch_t<DT_S3, 16>(a, s);
-    else launch_t<DT_FP8, 16>(a, s);
-  }
+  dispatch_form(dt, rows, [&](auto d, auto r, auto w) {
+    launch<decltype(d)::value, decltype(r)::value, decltype(w)::value>(a, s);
+  });
 }

@@ -26,7 +26,6 @@ ARCH = os.environ.get("DPPO_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 DEVICE_SRCS = ["rollout.hip", "eval.hip", "act.hip", "envstep.hip", "mlp.hip", "mlp_head.hip", "phead.hip", "wgrad.hip", "optim.hip", "obs.hip"]
 HOST_SRCS = ["bindings.cpp", "comm.cpp"]   # compiled with the torch include paths
-HEADERS = ["common.h", "mlp_core.h", "kernels.h", "t32.h"]
 
 
 def ext_path(variant: str = "") -> str:
@@ -73,7 +72,9 @@ def device_flags(extra=()) -> list:
 
 def _compile(src: str, cflags, verbose: bool, csrc: str = CSRC, extra=()) -> str:
     srcp = os.path.join(csrc, src)
-    deps = [srcp] + [os.path.join(csrc, h) for h in HEADERS]
+    # every header of the tree being built enters the key (a source includes any of them, and an
+    # older csrc/ built as a variant has its own set)
+    deps = [srcp] + sorted(os.path.join(csrc, h) for h in os.listdir(csrc) if h.endswith(".h"))
     flags = device_flags(extra) + cflags
     key = _digest(deps, " ".join(flags))
     obj = os.path.join(BUILD, f"{os.path.splitext(src)[0]}-{key}.o")
