@@ -134,8 +134,9 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   a.T = (int)ints[5]; a.t_base = (int)ints[6]; a.buf_E = (int)ints[7]; a.t0 = (uint32_t)ints[8];
   a.limit = (int)ints[9];
   TORCH_CHECK(a.E > 0 && a.T >= 1 && a.buf_E == a.E, "bad E/T");
-  TORCH_CHECK(a.kind == 0 || a.kind == 1, "kind");
-  TORCH_CHECK(a.kind == 0 ? a.S == a.O : (a.S == 2 && a.O == 3), "state dims");
+  TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
+  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
+              "state dims");
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
   const int nblk = (a.E + (int)rows - 1) / (int)rows;
   check(state, "state", at::kFloat, (int64_t)a.E * a.S);
@@ -256,9 +257,10 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
   TORCH_CHECK(ints[5] >= 1 && ints[5] <= (int64_t)1 << 20, "limit must be in [1, 2^20], got ", ints[5]);
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.limit = (int)ints[5]; a.deterministic = ints[7] ? 1 : 0;
-  TORCH_CHECK(a.kind == 0 || a.kind == 1, "kind");
+  TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
   TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
-  TORCH_CHECK(a.kind == 0 ? a.S == a.O : (a.S == 2 && a.O == 3), "state dims");
+  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
+              "state dims");
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
   a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[6] ? 1 : 0, qscale);
   check(mean, "mean", at::kFloat, a.O);

@@ -1,7 +1,8 @@
 // The in-kernel envs' physics, written once: the rollout kernel (csrc/rollout.hip) and the
 // evaluation kernel (csrc/eval.hip) both step their envs with these, so the two are bit-equal by
 // construction and both are held to the same torch env (envs/vec_env.py).  kind 0: the synthetic
-// S = O dim env; kind 1: the pendulum (state (th, thdot), obs (cos th, sin th, thdot)).
+// S = O dim env; kind 1: the pendulum (state (th, thdot), obs (cos th, sin th, thdot)); kind 2: the
+// continuous cart-pole (state = obs = (x, x_dot, th, th_dot), terminal on the NEW state).
 // The env state is a [ROWS][S] fp32 tile in LDS; `act` the [ROWS][A] actions of the step.
 #pragma once
 #include <type_traits>
@@ -13,6 +14,17 @@ constexpr float SYN_DECAY = 0.9f, SYN_DRIVE = 0.1f, SYN_NOISE = 0.05f, SYN_RESET
 constexpr float SYN_TERM_P = 0.002f;
 constexpr float ENV_PI = 3.14159265358979f, ENV_2PI = 6.28318530717959f;
 constexpr uint32_t RESET_STEP_KEY = 0xFFFFFFFFu;   // VecEnv.reset()'s step key
+constexpr int KIND_CARTPOLE = 2;
+// CartPoleContinuousEnv's constants (envs/vec_env.py), each the fp32 rounding of the double the
+// torch env multiplies its fp32 tensors with
+constexpr float CP_GRAVITY = 9.8f, CP_HALF_LEN = 0.5f, CP_FORCE_MAG = 10.f, CP_DT = 0.02f;
+constexpr float CP_MASS_POLE = 0.1f;
+constexpr float CP_TOTAL_MASS = (float)(1.0 + 0.1);   // MASS_CART + MASS_POLE, summed in double
+constexpr float CP_PML = (float)(0.1 * 0.5);          // MASS_POLE * HALF_LEN
+constexpr float CP_FOUR_THIRDS = (float)(4.0 / 3.0);
+constexpr float CP_X_LIMIT = 2.4f;
+constexpr float CP_THETA_LIMIT = (float)(12.0 * 2.0 * 3.14159265358979323846 / 360.0);
+constexpr float CP_RESET_RANGE = 0.05f;
 
 // observation of env r, dim d.  KIND is a template parameter: with a runtime kind the
 // pendulum's libm cosf/sinf (Payne-Hanek reduction, divergent per lane) was inlined into each
@@ -49,11 +61,65 @@ DEV float syn_err_term(float av, float sv) {
   const float d = ac - fast_tanh(sv);
   return d * d;
 }
+// The cart-pole: CartPoleContinuousEnv._dynamics (envs/vec_env.py) operation for operation, in
+// its order, every operation rounded to fp32 on its own (no contraction into FMAs): it differs
+// from the torch env's unfused ops only in the ulps of sinf / cosf (and of a division where the
+// torch device multiplies by a scalar's reciprocal).
+struct CartPoleState { float x, xd, th, thd; };
+DEV CartPoleState cartpole_next(const float* s, float a0) {
+#pragma clang fp contract(off)
+  const float x = s[0], xd = s[1], th = s[2], thd = s[3];
+  const float force = CP_FORCE_MAG * fminf(fmaxf(a0, -1.f), 1.f);
+  const float c = cosf(th), sn = sinf(th);
+  const float temp = (force + CP_PML * thd * thd * sn) / CP_TOTAL_MASS;
+  const float thacc = (CP_GRAVITY * sn - c * temp) /
+                      (CP_HALF_LEN * (CP_FOUR_THIRDS - CP_MASS_POLE * c * c / CP_TOTAL_MASS));
+  const float xacc = temp - CP_PML * thacc * c / CP_TOTAL_MASS;
+  CartPoleState n;
+  n.x = x + CP_DT * xd;
+  n.xd = xd + CP_DT * xacc;
+  n.th = th + CP_DT * thd;
+  n.thd = thd + CP_DT * thacc;
+  return n;
+}
+DEV bool cartpole_terminal(const CartPoleState& n) {
+  return fabsf(n.x) > CP_X_LIMIT || fabsf(n.th) > CP_THETA_LIMIT;
+}
+// reset of tile row r (env e) keyed (reset key, e, step): every dim uniform in +-CP_RESET_RANGE
+DEV void cartpole_reset(float* st, int S, int r, uint32_t key_reset, uint32_t e, uint32_t step) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+    st[r * S + d] = (2.f * uniform01(keyed(key_reset, e, step, (uint32_t)d)) - 1.f) * CP_RESET_RANGE;
+}
+
 // unclipped reward and termination of env e (tile row r) for this step's action; err: the
-// synthetic env's sum of syn_err_term over its na dims (unused by the pendulum)
-DEV float env_reward(int kind, const float* st, int S, const float* act, int A, int r, float err, int na,
+// synthetic env's sum of syn_err_term over its na dims (unused by the pendulum and the cart-pole).
+// Kinds 0 / 1 only read st.  The cart-pole ADVANCES its row here: see below.
+DEV float env_reward(int kind, float* st, int S, const float* act, int A, int r, float err, int na,
                      uint32_t key_term, uint32_t e, uint32_t kstep, bool& term) {
   term = false;
+  if (kind == KIND_CARTPOLE) {
+    // Terminal on the NEW state.  The step is computed once, here, and stashed in LDS for
+    // env_transition, not recomputed there: two inlined copies of the step give the same bits only
+    // as long as the compiler treats libm's sinf / cosf (whose operations carry their own
+    // contraction flags) the same way in both, and no test can see a done flag and a stored state
+    // that disagree by an ulp at a threshold.  One computation cannot disagree with itself, and it
+    // is one sinf / cosf pair per env and step, not two.  The stash is the env's own state row:
+    // in the kernels' phase (d) this lane is the row's only reader (the other lanes of the env
+    // read st for the synthetic reward only) and nothing reads st between here and phase (e), so
+    // the four floats the flag came from ARE the new state, env_transition only overwrites the
+    // rows whose done flag is set, and the stash costs no LDS and no pointer (a separate
+    // [ROWS][4] tile cost every instantiation of both kernels 2-3 VGPRs).
+    float* row = st + r * S;
+    const CartPoleState n = cartpole_next(row, act[r * A]);
+    row[0] = n.x;
+    row[1] = n.xd;
+    row[2] = n.th;
+    row[3] = n.thd;
+    term = cartpole_terminal(n);
+    return 1.f;
+  }
   if (kind == 1) {
     float th = st[r * S], thd = st[r * S + 1];
     float u = fminf(fmaxf(act[r * A], -2.f), 2.f);
@@ -111,10 +177,18 @@ template <int ROWS, int NTHR>
 DEV void env_transition(int kind, float* st, int S, const float* act, int A, const float* done_s,
                         const uint32_t* kes, const float* wdrv, const int* jdx, uint32_t key_reset, int e0,
                         uint32_t kstep, int tid) {
-  if (kind == 1) {
+  // the one-lane-per-env kinds share one branch (and one `tid < ROWS` region): a second top-level
+  // branch for the cart-pole tipped two 4-wave per-step-filter forms of the rollout kernel, 3 and 4
+  // VGPRs under 256, into AGPR spills
+  if (kind != 0) {
     if (tid < ROWS) {
-      if (done_s[tid] > 0.5f) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
-      else pend_step(st, S, tid, act[tid * A]);
+      const bool done = done_s[tid] > 0.5f;
+      if (kind == 1) {
+        if (done) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
+        else pend_step(st, S, tid, act[tid * A]);
+      } else if (done) {   // cart-pole: the rows already hold their new state (env_reward), only the resets are left
+        cartpole_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
+      }
     }
     return;
   }
@@ -165,8 +239,11 @@ DEV void env_transition(int kind, float* st, int S, const float* act, int A, con
 // Fresh envs for every row of the tile, as VecEnv.reset() (step key RESET_STEP_KEY)
 template <int ROWS, int NTHR>
 DEV void env_reset_fresh(int kind, float* st, int S, uint32_t key_reset, int e0, int tid) {
-  if (kind == 1) {
-    if (tid < ROWS) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), RESET_STEP_KEY);
+  if (kind != 0) {
+    if (tid < ROWS) {
+      if (kind == 1) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), RESET_STEP_KEY);
+      else cartpole_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), RESET_STEP_KEY);
+    }
     return;
   }
   const int np = (S + 1) >> 1;

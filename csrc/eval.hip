@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
       const int r = tid / LPE, l = tid - r * LPE;
       float err = 0.f;
       const int na = min(A, O);
-      if (a.kind != 1) {
+      if (a.kind == 0) {
         for (int j = l; j < na; j += LPE) err += syn_err_term(act[r * A + j], L.st[r * S + j]);
       }
 #pragma unroll

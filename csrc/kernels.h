@@ -20,7 +20,7 @@ struct PolicyNet {
 
 struct RolloutArgs {
   // env (state lives in global memory between launches, in LDS during the launch)
-  int kind;            // 0 synthetic, 1 pendulum
+  int kind;            // 0 synthetic, 1 pendulum, 2 cart-pole (csrc/env_core.h)
   int E, O, A, S;      // envs, obs dims, act dims, state dims
   int T;               // steps in this launch
   int t_base;          // buffer time index of the first step
@@ -83,7 +83,7 @@ inline __host__ __device__ size_t sn_g1_elems(int nblk, int O) {
 // Batched policy evaluation (csrc/eval.hip): E fresh envs, each from its reset to the end of its
 // first episode.  The env state lives in LDS only; the launch writes ret / len and nothing else.
 struct EvalArgs {
-  int kind;            // 0 synthetic, 1 pendulum
+  int kind;            // 0 synthetic, 1 pendulum, 2 cart-pole (csrc/env_core.h)
   int E, O, A, S;      // envs, obs dims, act dims, state dims
   int limit;           // episode step limit (the launch's loop bound)
   int deterministic;   // 1: a = mu, 0: a = mu + sigma * eps (eps keyed: action key, env, step)

@@ -423,7 +423,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
       const int na = min(A, O);
       for (int j = l; j < A; j += LPE) {
         lp += logp_term(L.epsb[r * A + j], L.lsg[j]);
-        if (a.kind != 1 && j < na) err += syn_err_term(L.act[r * A + j], L.st[r * S + j]);
+        if (a.kind == 0 && j < na) err += syn_err_term(L.act[r * A + j], L.st[r * S + j]);
       }
 #pragma unroll
       for (int o = LPE / 2; o > 0; o >>= 1) {

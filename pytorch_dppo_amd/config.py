@@ -46,6 +46,10 @@ class Params:
     device: str = "cpu"                  # cpu | gpu
     env_backend: str = "builtin"         # builtin (tensor envs: in-kernel on GPU when the rollout kernel knows the
                                          # kind, device-stepped otherwise) | gym (gym.make, host-stepped)
+    env_fused: bool = False              # GPU engine: run an env that has an in-kernel twin (VecEnv.kernel_kind) inside the
+                                         # rollout / evaluation kernels; changes nothing for the synthetic envs and the
+                                         # pendulum (always in-kernel), moves CartPoleContinuous-v1 off the device-stepped
+                                         # path; an env without a kernel kind is refused.  The CPU engine ignores it.
     env_module: str = ""                 # dotted module path imported once at start (worker, evaluator process,
                                          # play.py) so that it can call envs.register_tensor_env; "" = none
     host_policy: str = "torch"           # env_backend gym on the GPU engine, the per-step policy: torch (fp32 tensor
@@ -143,6 +147,8 @@ class Params:
             raise ValueError(f"device must be cpu|gpu, got {self.device}")
         if self.env_backend not in ("builtin", "gym"):
             raise ValueError(f"env_backend must be builtin|gym, got {self.env_backend}")
+        if self.env_fused and self.env_backend == "gym":
+            raise ValueError("env_fused runs a builtin env inside the rollout kernel; env_backend=gym is host-stepped")
         if self.host_policy not in ("torch", "kernel"):
             raise ValueError(f"host_policy must be torch|kernel, got {self.host_policy}")
         if self.dtype not in ("fp32", "bf16x3", "bf16", "fp8"):

@@ -9,7 +9,8 @@ env name resolves to
   used for every MuJoCo/Bullet name, or
 * ``tensor`` — a ``VecEnv`` subclass registered with :func:`register_tensor_env` (by this package:
   ``CartPoleContinuous-v1``; by a user's ``--env-module``): torch ops on device tensors, stepped on
-  the device by the GPU engine (``HipEngine.rollout_stepped``), or
+  the device by the GPU engine (``HipEngine.rollout_stepped``); the cart-pole also has an in-kernel
+  twin (kernel kind ``KIND_CARTPOLE``, ``--env-fused true``), or
 * ``gym`` — the real env through :mod:`pytorch_dppo_amd.envs.gym_adapter` with
   ``--env-backend gym`` (``gym.make``, or a factory installed with ``register_env``); its dims
   come from the env's spaces (:func:`host_spec`).
@@ -25,6 +26,10 @@ KIND_PENDULUM = 1
 KIND_HOST = 2          # a host-stepped env (gym backend): dims come from the env itself
 KIND_TENSOR = 3        # a registered tensor env (register_tensor_env): a VecEnv subclass the rollout kernel
                        # does not know; the GPU engine steps it on the device (HipEngine.rollout_stepped)
+# In-kernel env kinds of the rollout / evaluation kernels (csrc/env_core.h): KIND_SYNTHETIC, KIND_PENDULUM and
+KIND_CARTPOLE = 2      # the continuous cart-pole.  A kernel kind is what a VecEnv class can run as
+                       # (VecEnv.kernel_kind); it is not a spec kind: the cart-pole's spec stays KIND_TENSOR, and
+                       # the spec kind with the same number, KIND_HOST, never reaches a kernel.
 
 
 @dataclass(frozen=True)
@@ -86,6 +91,18 @@ def tensor_env_class(name: str):
     if name not in _TENSOR_ENVS:
         raise KeyError(f"no tensor env registered as {name!r}; registered: {sorted(_TENSOR_ENVS)}")
     return _TENSOR_ENVS[name]
+
+
+def kernel_kind_of(env) -> int:
+    """the in-kernel kind (KIND_SYNTHETIC / KIND_PENDULUM / KIND_CARTPOLE) ``env`` can run as inside the
+    rollout and evaluation kernels; ``ValueError`` naming the env when it has none"""
+    kind = getattr(env, "kernel_kind", None)
+    if kind is None:
+        spec = getattr(env, "spec", None)
+        name = getattr(spec, "name", "") or type(env).__name__
+        raise ValueError(f"env {name!r} ({type(env).__name__}) has no in-kernel twin (kernel_kind is None): "
+                         "it runs device-stepped (HipEngine.rollout_stepped), not with env_fused")
+    return int(kind)
 
 
 def import_env_module(module: str) -> None:

@@ -18,7 +18,7 @@ from typing import Dict, Tuple
 import torch
 
 from ..utils import rng
-from .registry import KIND_PENDULUM, KIND_SYNTHETIC, KIND_TENSOR, EnvSpec, register_tensor_env, tensor_env_class
+from .registry import KIND_CARTPOLE, KIND_PENDULUM, KIND_SYNTHETIC, KIND_TENSOR, EnvSpec, register_tensor_env, tensor_env_class
 
 SYN_DECAY = 0.9
 SYN_DRIVE = 0.1
@@ -34,6 +34,10 @@ def syn_weights(obs_dim: int, device) -> torch.Tensor:
 
 class VecEnv:
     """Base: E envs of one spec, keyed RNG (seed, rank)."""
+    # the in-kernel kind this class can run as inside the rollout / evaluation kernels (csrc/env_core.h),
+    # None when the kernels have no twin of it (every user env; envs.registry.kernel_kind_of).  A subclass
+    # that changes the dynamics of an env with a twin sets it back to None.
+    kernel_kind = None
 
     def __init__(self, spec: EnvSpec, num_envs: int, seed: int = 1, rank: int = 0,
                  device="cpu", max_episode_length: int = 10000):
@@ -120,6 +124,7 @@ class SyntheticEnv(VecEnv):
         terminal with probability 0.002 per step; reset s ~ 0.1 N(0,1)
     All noise is keyed (seed, rank, env, step, dim) — identical in ``csrc/rollout.hip``.
     """
+    kernel_kind = KIND_SYNTHETIC
 
     @property
     def state_dim(self) -> int:
@@ -153,6 +158,7 @@ class SyntheticEnv(VecEnv):
 class PendulumEnv(VecEnv):
     """gym Pendulum-v0 dynamics (g=10, m=l=1, dt=.05, max_speed 8, max_torque 2, 200 steps)."""
     G, M, L, DT, MAX_SPEED, MAX_TORQUE = 10.0, 1.0, 1.0, 0.05, 8.0, 2.0
+    kernel_kind = KIND_PENDULUM
 
     @property
     def state_dim(self) -> int:
@@ -190,9 +196,13 @@ class CartPoleContinuousEnv(VecEnv):
 
     state == observation (x, x_dot, theta, theta_dot).  Reward 1 per step; terminal when the NEW
     state has |x| > 2.4 or |theta| > 12 degrees; reset draws every state dim uniform in +-0.05 from
-    the keyed reset stream (dims 0..3).  A registered tensor env (``CartPoleContinuous-v1``, kind
-    KIND_TENSOR): the rollout kernel does not know it, the GPU engine steps it on the device
-    (HipEngine.rollout_stepped)."""
+    the keyed reset stream (dims 0..3).  A registered tensor env (``CartPoleContinuous-v1``, spec kind
+    KIND_TENSOR): by default the GPU engine steps it on the device (HipEngine.rollout_stepped).  It
+    also has an in-kernel twin, kernel kind KIND_CARTPOLE (csrc/env_core.h ``cartpole_next``: this
+    ``_dynamics`` operation for operation, compiled without FMA contraction), which ``env_fused``
+    (``--env-fused true``) selects: rollout and evaluation then run in the fused kernels, the done flag
+    of a step coming from the very four values the kernel stores as the new state."""
+    kernel_kind = KIND_CARTPOLE
     GRAVITY, MASS_CART, MASS_POLE, HALF_LEN, FORCE_MAG, DT = 9.8, 1.0, 0.1, 0.5, 10.0, 0.02
     X_LIMIT = 2.4
     THETA_LIMIT = 12.0 * 2.0 * math.pi / 360.0

@@ -27,7 +27,7 @@ from typing import Dict, Optional
 import torch
 
 from ..config import Params
-from ..envs.registry import KIND_PENDULUM, KIND_SYNTHETIC
+from ..envs.registry import KIND_PENDULUM, KIND_SYNTHETIC, kernel_kind_of
 from ..models.actor_critic import ActorCritic, PackedLayout, fm_index
 from ..ops import native, storage
 from ..utils import rng
@@ -348,7 +348,20 @@ class HipEngine:
         # a builtin (tensor) env of a kind the rollout / eval kernels do not run — a registered tensor
         # env (envs.register_tensor_env): rollout() and evaluate() step it on the device instead
         # (rollout_stepped: per step one act launch, the env's own torch ops, one env_advance launch)
-        self.stepped_env = not self.host_env and env.kind not in (KIND_SYNTHETIC, KIND_PENDULUM)
+        # params.env_fused: an env whose class has an in-kernel twin (VecEnv.kernel_kind: the cart-pole)
+        # runs inside the rollout / eval kernels as that kind instead; an env without one is refused
+        # here, not stepped quietly (kernel_kind_of raises, naming it).  rollout_stepped() keeps
+        # working on such an env: it is the second reference of the fused cart-pole's tests.
+        self.kernel_kind: Optional[int] = None      # the kind the kernels are launched with (None: none)
+        if self.host_env:
+            if bool(getattr(params, "env_fused", False)):
+                raise ValueError("env_fused runs a builtin env inside the rollout kernel; a host-stepped (gym) env "
+                                 "has no in-kernel dynamics")
+        elif env.kind in (KIND_SYNTHETIC, KIND_PENDULUM):
+            self.kernel_kind = int(env.kind)
+        elif bool(getattr(params, "env_fused", False)):
+            self.kernel_kind = kernel_kind_of(env)
+        self.stepped_env = not self.host_env and self.kernel_kind is None
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -646,7 +659,7 @@ class HipEngine:
                         epstat: Optional[torch.Tensor] = None):
         e = self.env
         kp = e.kernel_params()
-        ints = [kp["kind"], self.E, self.O, self.A, e.state_dim, T, t_base, self.E, t0 & 0xFFFFFFFF,
+        ints = [self._kind(), self.E, self.O, self.A, e.state_dim, T, t_base, self.E, t0 & 0xFFFFFFFF,
                 kp["limit"], 1 if self.p.std_convention == "var" else 0]
         keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
         xt = xT if xT is not None else self.empty_x
@@ -655,6 +668,14 @@ class HipEngine:
                          self.actions, self.logp, self.rewards, self.dones,
                          self.mom if mom is None else mom, self.epstat if epstat is None else epstat, ints, keys,
                          float(self.p.reward_clip), self.qscale, xt, self.x_rows[0])
+
+    def _kind(self) -> int:
+        """the in-kernel env kind of the rollout / eval launches; an env that has none never gets here
+        through rollout() / evaluate() (``stepped_env``), so reaching this without one is a caller's error"""
+        if self.kernel_kind is None:
+            raise RuntimeError(f"env {self.env.spec.name!r} has no in-kernel dynamics selected (env_fused): the "
+                               "rollout / evaluation kernels cannot run it")
+        return self.kernel_kind
 
     def _stepnorm_fits(self) -> bool:
         """the per-step normalisation launch holds every env tile co-resident on this device"""
@@ -680,7 +701,7 @@ class HipEngine:
             raise RuntimeError("per-step observation normalisation launch timed out waiting for a workgroup")
         e = self.env
         kp = e.kernel_params()
-        ints = [kp["kind"], self.E, self.O, self.A, e.state_dim, self.T, 0, self.E, e.t & 0xFFFFFFFF,
+        ints = [self._kind(), self.E, self.O, self.A, e.state_dim, self.T, 0, self.E, e.t & 0xFFFFFFFF,
                 kp["limit"], 1 if self.p.std_convention == "var" else 0]
         keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
         self.ext.rollout_stepnorm(self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout,
@@ -830,8 +851,9 @@ class HipEngine:
     @torch.no_grad()
     def rollout_stepped(self) -> Dict:
         """T steps of a builtin tensor env stepped ON THE DEVICE by its own torch ops — the path of a
-        registered tensor env (``stepped_env``), whose dynamics the rollout kernel does not know.
-        It also runs kinds 0 / 1 (the tests hold it against the fused kernel there).  Per step,
+        registered tensor env (``stepped_env``), whose dynamics the rollout kernel does not know or
+        was not asked to run (``env_fused`` off).  It also runs the envs rollout() takes in-kernel:
+        kinds 0 / 1 and the fused cart-pole (the tests hold it against the fused kernel there).  Per step,
         all on the current stream and with no host sync:
 
           1. one csrc/act.hip launch: normalise ``obs``, policy MLP, keyed sample -> the step's
@@ -1034,7 +1056,7 @@ class HipEngine:
         e = self.env
         k = eval_keys(self.p.seed)
         limit = int(min(e.spec.time_limit, self.p.max_episode_length))
-        ints = [e.kind, E, self.O, self.A, e.state_dim, limit, 1 if self.p.std_convention == "var" else 0,
+        ints = [self._kind(), E, self.O, self.A, e.state_dim, limit, 1 if self.p.std_convention == "var" else 0,
                 1 if deterministic else 0]
         keys = [k["key_env"], k["key_term"], k["key_reset"], k["key_action"]]
         self.ext.eval_rollout(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data,

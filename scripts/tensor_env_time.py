@@ -1,6 +1,6 @@
 """Time the device-stepped rollout (HipEngine.rollout_stepped) per env step, three ways.
 
-    python scripts/tensor_env_time.py [--out tensor_env_time.json] [--rounds 7] [--reps 64]
+    python scripts/tensor_env_time.py [--out tensor_env_time.json] [--rounds 7] [--reps 64] [--env pendulum|cartpole]
 
 Pendulum-v0 (a kind the fused kernel also runs), E = 4096, T = 16, bf16x3, one process, three engines
 with the same weights, alternating round by round:
@@ -17,6 +17,9 @@ Two warm-up rollouts each, then a host clock around each window of ``--reps`` ro
 of the fused kernel's, so that its window is not a few milliseconds), which ends in a device
 synchronise, divided by the window's env steps.  Prints one JSON line (and writes it to
 ``--out``): the median, min and max over the rounds.  No threshold.
+
+``--env cartpole``: CartPoleContinuous-v1, the same sizes and method, variants (a) ``rollout_stepped()``
+(its default path) and (c) ``rollout()`` with ``env_fused`` (in-kernel env kind 2); there is no (b).
 """
 import argparse
 import json
@@ -37,11 +40,13 @@ from pytorch_dppo_amd.utils import rng  # noqa: E402
 from pytorch_dppo_amd.utils.obs_stats import RunningObsStats  # noqa: E402
 
 ENV, E, T, DTYPE = "Pendulum-v0", 4096, 16, "bf16x3"
+ENVS = {"pendulum": "Pendulum-v0", "cartpole": "CartPoleContinuous-v1"}
 FUSED_REPS_X = 16    # the fused kernel's rollouts per window, as a multiple of --reps
 
 
-def build(dev):
-    p = dppo_preset(device="gpu", env_name=ENV, num_envs=E, exploration_size=E * T, batch_size=E * T, dtype=DTYPE)
+def build(dev, env_fused=False):
+    p = dppo_preset(device="gpu", env_name=ENV, num_envs=E, exploration_size=E * T, batch_size=E * T, dtype=DTYPE,
+                    env_fused=env_fused)
     spec = get_spec(ENV)
     torch.manual_seed(0)
     model = ActorCritic(spec.obs_dim, spec.act_dim, p.hidden).to(dev)
@@ -95,19 +100,28 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=64, help="rollouts per timed window")
+    ap.add_argument("--env", choices=sorted(ENVS), default="pendulum")
     a = ap.parse_args()
+    global ENV
+    ENV = ENVS[a.env]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    engs = {k: build(dev) for k in ("a_env_advance", "b_torch_bookkeeping", "c_fused_kernel")}
-    fns = {"a_env_advance": engs["a_env_advance"].rollout_stepped,
-           "b_torch_bookkeeping": lambda: rollout_stepped_torch(engs["b_torch_bookkeeping"]),
-           "c_fused_kernel": engs["c_fused_kernel"].rollout}
+    if a.env == "cartpole":
+        engs = {"a_env_advance": build(dev), "c_fused_kernel": build(dev, env_fused=True)}
+        assert engs["a_env_advance"].stepped_env and not engs["c_fused_kernel"].stepped_env
+        fns = {"a_env_advance": engs["a_env_advance"].rollout_stepped, "c_fused_kernel": engs["c_fused_kernel"].rollout}
+    else:
+        engs = {k: build(dev) for k in ("a_env_advance", "b_torch_bookkeeping", "c_fused_kernel")}
+        fns = {"a_env_advance": engs["a_env_advance"].rollout_stepped,
+               "b_torch_bookkeeping": lambda: rollout_stepped_torch(engs["b_torch_bookkeeping"]),
+               "c_fused_kernel": engs["c_fused_kernel"].rollout}
     for fn in fns.values():          # warm-up (allocations, code objects, lazy inits)
         timed(fn, 2)
     # same seed, same keys: after the same number of rollouts the three engines hold the same env
     st = [engs[k].env.state for k in fns]
-    same = {"a_vs_b_state_equal": bool(torch.equal(st[0], st[1])),
-            "a_vs_c_state_max_gap": float((st[0] - st[2]).abs().max())}
+    same = {"a_vs_c_state_max_gap": float((st[0] - st[-1]).abs().max())}
+    if "b_torch_bookkeeping" in fns:
+        same["a_vs_b_state_equal"] = bool(torch.equal(st[0], st[1]))
     times = {k: [] for k in fns}
     for _ in range(a.rounds):        # alternate the variants round by round
         for k, fn in fns.items():
