@@ -202,6 +202,33 @@ void rollout(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len
   after_launch(__func__);
 }
 
+// rollout() with bootstrap_time_limit's outputs (csrc/rollout.hip FIN): trunc [t_base + T][E] fp32
+// gets 1 where an episode ended by the step limit alone, and x_fin [fin_K][E][d1] (x_out's storage
+// type, zeroed by the caller) the normalised observation such a step reached before its reset, at
+// row ((t_base + step) / limit) * E + e.  Every extent the kernel indexes is checked here.
+void rollout_fin(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
+                 torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
+                 torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor x_out,
+                 torch::Tensor actions, torch::Tensor logp, torch::Tensor rewards, torch::Tensor dones,
+                 torch::Tensor mom, torch::Tensor epstat, std::vector<int64_t> ints, std::vector<int64_t> keys,
+                 double reward_clip, torch::Tensor qscale, torch::Tensor xT_out, int64_t xT_rows, torch::Tensor trunc,
+                 torch::Tensor x_fin, int64_t fin_K) {
+  RolloutArgs a = rollout_args(dt, rows, state, ep_len, ep_ret, wimg, layout, scales, flat, mean, inv_std, shift,
+                               x_out, actions, logp, rewards, dones, mom, epstat, ints, keys, reward_clip, qscale,
+                               xT_out, xT_rows);
+  TORCH_CHECK(a.limit >= 1, "limit must be >= 1, got ", a.limit);
+  const int64_t steps = (int64_t)a.t_base + a.T;
+  TORCH_CHECK(fin_K >= 1 && fin_K <= std::numeric_limits<int>::max() && fin_K >= (steps + a.limit - 1) / a.limit,
+              "fin_K = ", fin_K, " is below ceil(T / limit) = ", (steps + a.limit - 1) / a.limit);
+  check(trunc, "trunc", at::kFloat, steps * a.E);
+  check(x_fin, "x_fin", storage_type(dt == 2 ? 1 : (int)dt), fin_K * a.E * a.net.d1);
+  a.trunc = trunc.data_ptr<float>();
+  a.x_fin = x_fin.data_ptr();
+  a.fin_K = (int)fin_K;
+  launch_rollout((int)dt, a, (int)rows, cur_stream());
+  after_launch(__func__);
+}
+
 // The per-step observation-normalisation rollout (obs_norm_update = "step") as ONE cooperative
 // launch (csrc/rollout.hip sn_step): `sn` = [mean f64, m2 f64, mean_f32, inv_std] of the stats the
 // steps absorb (updated in place), g1 / g2 the granule buffers (int64, zero-initialised once; tags
@@ -337,9 +364,11 @@ void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std
 // read; state, ep_len [E] int32, ep_ret [E] are updated in place; rewards_row / dones_row [E] and
 // epstat [ceil(E/16)][2] (overwritten with init, else added to) are written.  Every extent is exact:
 // the grid is sized from E alone.
-void env_advance(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new_state, torch::Tensor reset_state,
-                 torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret, torch::Tensor rewards_row,
-                 torch::Tensor dones_row, torch::Tensor epstat, int64_t limit, double reward_clip, bool init) {
+// fin (bootstrap_time_limit, env_advance_fin): {fin_src, fin_dst, trunc_row} or empty.
+void env_advance_impl(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new_state, torch::Tensor reset_state,
+                      torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret, torch::Tensor rewards_row,
+                      torch::Tensor dones_row, torch::Tensor epstat, int64_t limit, double reward_clip, bool init,
+                      const std::vector<torch::Tensor>& fin, const char* who) {
   TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(1) >= 1, "state must be [E][S] with E, S >= 1");
   const int64_t E = state.size(0), S = state.size(1);
   TORCH_CHECK(E <= (int64_t)1 << 30 && S < (int64_t)1 << 20, "E must be <= 2^30 and S < 2^20, got ", E, " x ", S);
@@ -374,8 +403,42 @@ void env_advance(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new
   a.rewards_row = rewards_row.data_ptr<float>();
   a.dones_row = dones_row.data_ptr<float>();
   a.epstat = epstat.data_ptr<float>();
+  if (!fin.empty()) {
+    const torch::Tensor &src = fin[0], &dst = fin[1], &tr = fin[2];
+    TORCH_CHECK(src.dim() == 2 && src.size(0) == E && src.size(1) >= 1, "fin_src must be [E][d1]");
+    const int64_t row_bytes = src.size(1) * src.element_size();
+    TORCH_CHECK(row_bytes % 16 == 0 && row_bytes < ((int64_t)1 << 20), "final rows must be a multiple of 16 bytes, "
+                "below 2^20, got ", row_bytes);
+    TORCH_CHECK(dst.scalar_type() == src.scalar_type(), "fin_dst has dtype ", dst.scalar_type(), ", fin_src ",
+                src.scalar_type());
+    exact(src, "fin_src", src.scalar_type(), E * src.size(1));
+    exact(dst, "fin_dst", src.scalar_type(), E * src.size(1));
+    exact(tr, "trunc_row", at::kFloat, E);
+    a.fin_src = src.data_ptr();
+    a.fin_dst = dst.data_ptr();
+    a.trunc_row = tr.data_ptr<float>();
+    a.fin_row_bytes = (int)row_bytes;
+  }
   launch_env_advance(a, cur_stream());
-  after_launch(__func__);
+  after_launch(who);
+}
+
+void env_advance(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new_state, torch::Tensor reset_state,
+                 torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret, torch::Tensor rewards_row,
+                 torch::Tensor dones_row, torch::Tensor epstat, int64_t limit, double reward_clip, bool init) {
+  env_advance_impl(reward, terminal, new_state, reset_state, state, ep_len, ep_ret, rewards_row, dones_row, epstat,
+                   limit, reward_clip, init, {}, __func__);
+}
+
+// env_advance with bootstrap_time_limit's outputs: trunc_row [E] gets 1 for an env that ended by the
+// step limit alone, and such an env's row of fin_src [E][d1] (its final observation, normalised, in
+// the buffer's storage type) is copied to fin_dst [E][d1], the caller's slice x_fin[t // limit].
+void env_advance_fin(torch::Tensor reward, torch::Tensor terminal, torch::Tensor new_state, torch::Tensor reset_state,
+                     torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret, torch::Tensor rewards_row,
+                     torch::Tensor dones_row, torch::Tensor epstat, int64_t limit, double reward_clip, bool init,
+                     torch::Tensor fin_src, torch::Tensor fin_dst, torch::Tensor trunc_row) {
+  env_advance_impl(reward, terminal, new_state, reset_state, state, ep_len, ep_ret, rewards_row, dones_row, epstat,
+                   limit, reward_clip, init, {fin_src, fin_dst, trunc_row}, __func__);
 }
 
 // the largest env-tile grid the per-step normalisation launch can run co-resident
@@ -834,6 +897,30 @@ void gae(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch
   after_launch(__func__);
 }
 
+// gae() with boot [T,E] (bootstrap_time_limit: V of a truncated step's final observation, 0 elsewhere;
+// an empty tensor: gae() itself)
+void gae_boot(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor adv,
+              torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
+  TORCH_CHECK(seg >= 0, "segment length must be >= 0 (0: no segment cut)");
+  TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "gae mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
+  const int64_t T = rewards.size(0), E = rewards.size(1);
+  check(rewards, "rewards", at::kFloat, T * E);
+  check(values, "values", at::kFloat, (T + 1) * E);
+  check(dones, "dones", at::kFloat, T * E);
+  check(adv, "adv", at::kFloat, T * E);
+  check(ret, "ret", at::kFloat, T * E);
+  const float* b = nullptr;
+  if (boot.defined() && boot.numel() > 0) {
+    check(boot, "boot", at::kFloat, T * E);
+    b = boot.data_ptr<float>();
+  }
+  launch_gae_boot(rewards.data_ptr<float>(), values.data_ptr<float>(), dones.data_ptr<float>(), b,
+                  adv.data_ptr<float>(), ret.data_ptr<float>(), (int)T, (int)E, (float)gamma, (float)lam, (int)mode,
+                  (int)seg, cur_stream());
+  after_launch(__func__);
+}
+
 void metrics_pack(torch::Tensor ep, torch::Tensor loss8, torch::Tensor norm_part, torch::Tensor out) {
   check(ep, "ep", at::kDouble, 2);
   check(loss8, "loss8", at::kFloat, 8);
@@ -982,10 +1069,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native DPPO kernels (gfx950 HIP)";
   register_comm(m);
   m.def("rollout", &rollout);
+  m.def("rollout_fin", &rollout_fin);
   m.def("rollout_stepnorm", &rollout_stepnorm);
   m.def("eval_rollout", &eval_rollout);
   m.def("policy_act", &policy_act);
   m.def("env_advance", &env_advance);
+  m.def("env_advance_fin", &env_advance_fin);
   m.def("rollout_stepnorm_cap", &rollout_stepnorm_cap_b);
   m.def("mlp_value", &mlp_value);
   m.def("mlp_train", &mlp_train);
@@ -1019,6 +1108,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_task_ok", [](int64_t dt, int64_t nq, int64_t kq) { return wgrad_task_ok((int)dt, (int)nq, (int)kq) != 0; });
   m.def("grad_gather", &grad_gather);
   m.def("gae", &gae);
+  m.def("gae_boot", &gae_boot);
   m.def("set_adam_fused", [](int64_t on) { set_adam_fused((int)on); });
   m.def("obs_reduce", &obs_reduce);
   m.def("obs_merge", &obs_merge);

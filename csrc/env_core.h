@@ -236,6 +236,30 @@ DEV void env_transition(int kind, float* st, int S, const float* act, int A, con
   }
 }
 
+// The in-place reset alone, of the rows whose flag is negative (the rollout kernel's truncated rows,
+// stepped as not done first so that their final observation could be read): env_transition's reset
+// expressions on the same keys, so the state is the bits its done branch would have left.
+template <int ROWS, int NTHR>
+DEV void env_reset_rows(int kind, float* st, int S, const float* flag_s, const uint32_t* kes, uint32_t key_reset,
+                        int e0, uint32_t kstep, int tid) {
+  if (kind != 0) {
+    if (tid < ROWS && flag_s[tid] < -0.5f) {
+      if (kind == 1) pend_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
+      else cartpole_reset(st, S, tid, key_reset, (uint32_t)(e0 + tid), kstep);
+    }
+    return;
+  }
+  const int np = (S + 1) >> 1;
+  for (int i = tid; i < ROWS * np; i += NTHR) {
+    const int r = i / np, p = i - r * np;
+    if (flag_s[r] < -0.5f) {
+      const float2 g = gauss_pair(kes[2 * ROWS + r], (uint32_t)p);
+      st[r * S + 2 * p] = SYN_RESET * g.x;
+      if (2 * p + 1 < S) st[r * S + 2 * p + 1] = SYN_RESET * g.y;
+    }
+  }
+}
+
 // Fresh envs for every row of the tile, as VecEnv.reset() (step key RESET_STEP_KEY)
 template <int ROWS, int NTHR>
 DEV void env_reset_fresh(int kind, float* st, int S, uint32_t key_reset, int e0, int tid) {

@@ -15,6 +15,11 @@
 // workgroup's [envs][S] state slab as one coalesced pass.  No atomics: every output element has one
 // owner, and a tile's sum is added by one thread in env order, so a launch is deterministic.  The
 // kernel's only global stores are the outputs listed in EnvStepArgs.
+//
+// bootstrap_time_limit (EnvStepArgs fin_*, trunc_row; null: none of this runs): an env that ended by
+// the step limit alone also gets trunc_row = 1 and its final-observation row (fin_src: the rows one
+// rows-only act launch made from observe(new_state)) copied into this step's x_fin slot (fin_dst),
+// 16 bytes per thread and turn.
 #include "kernels.h"
 #include "common.h"
 
@@ -36,14 +41,16 @@ __global__ __launch_bounds__(ES_ENVS) void env_advance_kernel(EnvStepArgs a) {
     const float r = a.reward[e];
     int el = a.ep_len[e] + 1;
     float er = a.ep_ret[e] + r;
-    const bool done = a.terminal[e] != 0 || el >= a.limit;
+    const bool term = a.terminal[e] != 0;
+    const bool done = term || el >= a.limit;
     if (done) {
       fr = er;
       fc = 1.f;
       el = 0;
       er = 0.f;
-      d = 1;
+      d = term ? 1 : 2;   // 2: truncated (read by the final-row copy below)
     }
+    if (a.trunc_row != nullptr) a.trunc_row[e] = d == 2 ? 1.f : 0.f;
     a.ep_len[e] = el;
     a.ep_ret[e] = er;
     const float c = a.reward_clip;
@@ -80,6 +87,13 @@ __global__ __launch_bounds__(ES_ENVS) void env_advance_kernel(EnvStepArgs a) {
     const int le = i / S;
     const float* src = dn[le] ? a.reset_state : a.new_state;
     a.state[base + i] = src[base + i];
+  }
+  if (a.fin_dst != nullptr) {
+    const int ch = a.fin_row_bytes >> 4;   // 16-byte chunks per row (the binding checks the multiple)
+    const uint4* src = static_cast<const uint4*>(a.fin_src) + (size_t)e0 * ch;
+    uint4* dst = static_cast<uint4*>(a.fin_dst) + (size_t)e0 * ch;
+    for (int i = tid; i < nenv * ch; i += ES_ENVS)   // (row bytes < 2^20: the binding checks)
+      if (dn[i / ch] == 2) dst[i] = src[i];
   }
 }
 

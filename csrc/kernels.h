@@ -67,6 +67,14 @@ struct RolloutArgs {
   double sn_n0;              // running count before step 0 (each step adds E)
   unsigned sn_epoch0;        // tag of step 0's granules (>= 1)
   double sn_var_floor;
+  // bootstrap_time_limit (both or neither; null: the kernel without them, sn_g1 must be null too).
+  // An episode that ends by the step limit alone (done && !terminal) is "truncated": trunc gets
+  // 1, and the normalised observation the env reached BEFORE its in-place reset is written, in
+  // x_out's row format, to x_fin row ((t_base + step) / limit) * E + e.  An env's truncations are
+  // >= limit steps apart, so that slot is its own: no counters, no atomics.
+  float* trunc;        // [T][E] 0.f / 1.f, like dones
+  void* x_fin;         // [fin_K][E][d1] storage precision (allocated zeroed by the host)
+  int fin_K;           // >= ceil((t_base + T) / limit)
 };
 
 // The per-step filter's partial-moment granules (RolloutArgs::sn_g1), line-blocked: a 128-byte
@@ -142,6 +150,13 @@ struct EnvStepArgs {
   float* rewards_row;  // [E]
   float* dones_row;    // [E] 0.f / 1.f
   float* epstat;       // [ceil(E/16)][2] (finished-episode return sum, count) per tile
+  // bootstrap_time_limit (all three or none; null: the kernel without them): an env that ended by
+  // the step limit alone (done && !terminal) gets trunc_row = 1 (else 0) and its row of fin_src
+  // copied to fin_dst
+  const void* fin_src; // [E][fin_row_bytes] the step's final observation rows (buffer precision)
+  void* fin_dst;       // [E][fin_row_bytes] the x_fin slot of this step
+  float* trunc_row;    // [E] 0.f / 1.f
+  int fin_row_bytes;   // bytes of one row (a multiple of 16)
 };
 
 // fp8 mode's gradient-amax ring (csrc/common.h Q8): [3 slots][4 tensors][Q8_SUB sub-slots][Q8_LINE]
@@ -307,6 +322,9 @@ void launch_grad_gather(const float* slab, const int* src_off, const int* src_me
                         const SlabRuns& runs, float* loss_out, hipStream_t s);
 void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
                 int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s);
+// boot: optional [T][E] value of a truncated step's final observation (null: launch_gae)
+void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot, float* adv,
+                     float* ret, int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s);
 void set_adam_fused(int on);
 void launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                  float eps, float max_norm, float* state, float* norm_part, int nblk,

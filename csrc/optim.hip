@@ -20,10 +20,14 @@ namespace {
 // depend on the dones BEFORE t, so a forward pass over the env's dones writes them into adv (as
 // scratch: each element is read back by the same thread before the reverse pass overwrites it).
 DEV bool seg_cut(int t, int td, int seg, float d) { return d == 0.f && (t - td) % seg == 0; }
+// BOOT: boot [T][E] (bootstrap_time_limit: V of the observation a step-limit episode end reached
+// before its reset, 0 elsewhere) enters delta only, delta_t = r_t + gamma*(V_{t+1}*(1-d_t) + boot_t) - V_t;
+// the recursion stays cut at the done.  !BOOT is the kernel without it, instruction for instruction.
+template <bool BOOT>
 __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, const float* __restrict__ val,
-                                                 const float* __restrict__ done, float* __restrict__ adv,
-                                                 float* __restrict__ ret, int T, int E, float gamma, float lam,
-                                                 int seg) {
+                                                 const float* __restrict__ done, const float* __restrict__ boot,
+                                                 float* __restrict__ adv, float* __restrict__ ret, int T, int E,
+                                                 float gamma, float lam, int seg) {
   const int e = blockIdx.x * 64 + threadIdx.x;
   if (e >= E) return;
   if (seg > 0) {
@@ -37,9 +41,9 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
   }
   float nxt = 0.f;
   float vnext = val[(size_t)T * E + e];
-  auto step = [&](size_t o, float r, float v, float d, float cont) {
+  auto step = [&](size_t o, float r, float v, float d, float cont, float b) {
     const float nt = 1.f - d;
-    const float delta = r + gamma * vnext * nt - v;
+    const float delta = BOOT ? r + gamma * (vnext * nt + b) - v : r + gamma * vnext * nt - v;
     nxt = delta + gamma * lam * nt * cont * nxt;
     adv[o] = nxt;
     ret[o] = nxt + v;
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
   };
   int t = T - 1;
   for (; t >= 7; t -= 8) {
-    float r[8], v[8], d[8], c[8];
+    float r[8], v[8], d[8], c[8], b[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const size_t o = (size_t)(t - k) * E + e;
@@ -55,13 +59,14 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
       v[k] = val[o];
       d[k] = done[o];
       c[k] = seg > 0 ? adv[o] : 1.f;
+      b[k] = BOOT ? boot[o] : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) step((size_t)(t - k) * E + e, r[k], v[k], d[k], c[k]);
+    for (int k = 0; k < 8; ++k) step((size_t)(t - k) * E + e, r[k], v[k], d[k], c[k], b[k]);
   }
   for (; t >= 0; --t) {
     const size_t o = (size_t)t * E + e;
-    step(o, rew[o], val[o], done[o], seg > 0 ? adv[o] : 1.f);
+    step(o, rew[o], val[o], done[o], seg > 0 ? adv[o] : 1.f, BOOT ? boot[o] : 0.f);
   }
 }
 
@@ -73,10 +78,11 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
 // exclusive scan over the 256 chunk maps (in LDS, Hillis-Steele) gives each chunk its incoming
 // A_{t1}, and every thread replays its chunk to write adv / ret.  Same arithmetic per step as
 // gae_kernel; only the association of the products differs (fp32 rounding-level).
+template <bool BOOT>
 __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__ rew, const float* __restrict__ val,
-                                                       const float* __restrict__ done, float* __restrict__ adv,
-                                                       float* __restrict__ ret, int T, int E, float gamma,
-                                                       float lam, int seg) {
+                                                       const float* __restrict__ done, const float* __restrict__ boot,
+                                                       float* __restrict__ adv, float* __restrict__ ret, int T, int E,
+                                                       float gamma, float lam, int seg) {
   __shared__ float sD[256], sC[256];
   __shared__ int sT[256];
   const int e = blockIdx.x, j = threadIdx.x;
@@ -107,7 +113,8 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
   auto delta_c = [&](int t, float& delta, float& c) {
     const size_t o = (size_t)t * E + e;
     const float nt = 1.f - done[o];
-    delta = rew[o] + gamma * val[o + E] * nt - val[o];
+    if constexpr (BOOT) delta = rew[o] + gamma * (val[o + E] * nt + boot[o]) - val[o];
+    else delta = rew[o] + gamma * val[o + E] * nt - val[o];
     c = gamma * lam * nt * (seg > 0 ? adv[o] : 1.f);
   };
   float D = 0.f, C = 1.f;
@@ -535,18 +542,29 @@ extern "C" void launch_metrics_pack(const double* ep, const float* loss8, const 
   HIP_CHECK_LAUNCH();
 }
 
-extern "C" void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
-                           int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s) {
+// boot: optional [T][E] (null: the kernels without it)
+extern "C" void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot,
+                                float* adv, float* ret, int T, int E, float gamma, float lam, int mode, int seg,
+                                hipStream_t s) {
   // mode 0 = auto: the per-env lane scan keeps >= 1 full wave busy per env batch; with few envs
   // and a long horizon its single dependent chain per lane is the latency, so scan in time.
   const bool scan = mode == 2 || (mode == 0 && E <= 64 && T >= 512);
-  if (scan)
-    hipLaunchKernelGGL(gae_scan_kernel, dim3(E), dim3(256), 0, s, rewards, values, dones, adv, ret, T, E, gamma, lam,
-                       seg);
-  else
-    hipLaunchKernelGGL(gae_kernel, dim3((E + 63) / 64), dim3(64), 0, s, rewards, values, dones, adv, ret, T, E,
-                       gamma, lam, seg);
+  const dim3 grid = scan ? dim3(E) : dim3((E + 63) / 64), block = scan ? dim3(256) : dim3(64);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, rewards, values, dones, boot, adv, ret, T, E, gamma, lam, seg);
+  };
+  if (boot != nullptr) {
+    if (scan) go(gae_scan_kernel<true>);
+    else go(gae_kernel<true>);
+  } else {
+    if (scan) go(gae_scan_kernel<false>);
+    else go(gae_kernel<false>);
+  }
   HIP_CHECK_LAUNCH();
+}
+extern "C" void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
+                           int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s) {
+  launch_gae_boot(rewards, values, dones, nullptr, adv, ret, T, E, gamma, lam, mode, seg, s);
 }
 
 static int g_adam_fused = 1;   // A/B switch (set_adam_fused): 0 forces the sumsq + adam pair

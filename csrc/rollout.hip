@@ -199,13 +199,17 @@ struct RolloutLds {
 // form (2 waves per SIMD) doubles the threads of the VALU-heavy observe / sample / env phases
 // and gives the SIMDs a second wave to hide latency with; the MFMA layers use the first waves.
 // SN: per-step observation normalisation inside the launch (RolloutArgs sn_*; cooperative launch)
-template <int DT, int ROWS, int NW, bool SN>
+// FIN: bootstrap_time_limit (RolloutArgs trunc / x_fin): step (d) marks the rows that ended by the
+// step limit alone, step (e) takes a cold branch for a tile that has one.  A template parameter so
+// that the forms without it keep their instructions and registers; never together with SN.
+template <int DT, int ROWS, int NW, bool SN, bool FIN>
 __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
   using P = Prec<DT>;
   using T = typename P::T;
   constexpr int NTHR = 64 * NW;
   static_assert(ROWS % 4 == 0 && NTHR % ROWS == 0 && (NTHR / ROWS) <= 64, "rollout tiling");
   static_assert(!SN || NW >= 4, "the per-step filter's reduce polls with waves 0-3");
+  static_assert(!(SN && FIN), "the final rows are normalised with the launch's fixed statistics");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e0 = blockIdx.x * ROWS;
   const int nvalid = min(ROWS, a.E - e0);
@@ -444,9 +448,12 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
         }
         L.eplen[r] = el;
         L.epret[r] = er_;
-        L.done_s[r] = done ? 1.f : 0.f;
+        // FIN: done_s 2 marks a truncated row (terminal wins; the pad rows of the last tile never)
+        const bool tr = FIN && done && !term && r < nvalid;
+        L.done_s[r] = done ? (tr ? 2.f : 1.f) : 0.f;
         if (r < nvalid) {
           size_t o = (size_t)tb * a.buf_E + e;
+          if constexpr (FIN) a.trunc[o] = tr ? 1.f : 0.f;
           float rc = rew;
           if (a.reward_clip > 0.f) rc = fminf(fmaxf(rc, -a.reward_clip), a.reward_clip);
           a.logp[o] = lp;
@@ -458,7 +465,55 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
     __syncthreads();
     PH(5);   // (d) logp / reward
     // ---- (e) state transition (+ in-place reset on done) ----
+    bool anyt = false;   // workgroup-uniform: every thread reads the same ROWS flags
+    if constexpr (FIN) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) anyt |= L.done_s[r] > 1.5f;
+    }
+    // cold (anyt): some row of the tile is truncated.  Its final observation is of the state the
+    // env reached, which the transition would replace by the reset: the truncated rows are stepped
+    // as not done (flag -1), their normalised rows go to x_fin, then exactly those rows are reset.
+    // The resets depend only on (reset key, env, step): st ends up the same bits either way, and
+    // the transition is the one call for both paths.
+    if (anyt) {
+      __syncthreads();   // (every thread has read the flags)
+      if (tid < ROWS && L.done_s[tid] > 1.5f) L.done_s[tid] = -1.f;
+      __syncthreads();
+    }
     env_transition<ROWS, NTHR>(a.kind, L.st, S, L.act, A, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
+    if (anyt) {
+      __syncthreads();
+      // the rows as step (a) makes them, through the input tile (free until the next observe):
+      // same norm_clamp / pad_col / storage conversion, so the 16-byte row stores are step (a)'s too
+      auto final_rows = [&](auto kind_tag) {
+        constexpr int KIND = decltype(kind_tag)::value;
+        for (int i = tid; i < ROWS * d1; i += NTHR) {
+          const int r = i / d1, d = i - r * d1;
+          if (L.done_s[r] < -0.5f) {
+            const float xv = d < O ? norm_clamp(env_obs<KIND>(L.st, S, r, d), a.mean[d], a.inv_std[d]) : pad_col(d, O);
+            P::put(L.t.xs, r * ld1 + d, xv);
+            if constexpr (STAGE) L.xsb[r * d1 + d] = PX::cvt(xv);
+          }
+        }
+      };
+      env_kind_switch(a.kind, final_rows);
+      __syncthreads();
+      const int slot = tb / a.limit;
+      if (slot < a.fin_K) {
+        typename PX::T* xf = reinterpret_cast<typename PX::T*>(a.x_fin) + ((size_t)slot * a.E + e0) * d1;
+        constexpr int EPC = 16 / sizeof(typename PX::T);
+        const int ch = d1 / EPC;
+        for (int i = tid; i < nvalid * ch; i += NTHR) {
+          const int r = i / ch, c = i - r * ch;
+          if (L.done_s[r] < -0.5f) {
+            const void* src = STAGE ? static_cast<const void*>(L.xsb + r * d1 + c * EPC)
+                                    : static_cast<const void*>(L.t.xs + r * ld1 + c * EPC);
+            *reinterpret_cast<uint4*>(xf + (size_t)r * d1 + c * EPC) = *reinterpret_cast<const uint4*>(src);
+          }
+        }
+      }
+      env_reset_rows<ROWS, NTHR>(a.kind, L.st, S, L.done_s, L.kes, a.key_reset, e0, kstep, tid);
+    }
     __syncthreads();
     PH(6);   // (e) env transition
   }
@@ -504,10 +559,10 @@ auto dispatch_form(int dt, int rows, F&& f) {
 }
 
 // the launch's dynamic-LDS bytes (and the kernel's attribute for them)
-template <int DT, int ROWS, int NW, bool SN>
+template <int DT, int ROWS, int NW, bool SN, bool FIN = false>
 size_t launch_lds(const RolloutArgs& a) {
   const size_t lds = RolloutLds<DT, ROWS, SN>(nullptr, a).cv.off;
-  if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, SN>>(lds);
+  if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, SN, FIN>>(lds);
   return lds;
 }
 
@@ -520,7 +575,7 @@ template <int DT, int ROWS, int NW>
 hipError_t stepnorm_cap(const RolloutArgs& a, size_t lds, int& cap) {
   int per_cu = 0, dev = 0, ncu = 0;
   hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true>), NW * 64, lds);
+      &per_cu, reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true, false>), NW * 64, lds);
   if (e == hipSuccess) e = hipGetDevice(&dev);
   if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   cap = ncu * (per_cu > 1 ? per_cu - 1 : per_cu);
@@ -533,9 +588,18 @@ template <int DT, int ROWS, int NW>
 void launch(const RolloutArgs& a, hipStream_t s) {
   const int nblk = (a.E + ROWS - 1) / ROWS;
   if (a.sn_g1 == nullptr) {
-    const size_t lds = launch_lds<DT, ROWS, NW, false>(a);
-    hipLaunchKernelGGL((rollout_kernel<DT, ROWS, NW, false>), dim3(nblk), dim3(NW * 64), lds, s, a);
+    if (a.x_fin != nullptr) {
+      const size_t lds = launch_lds<DT, ROWS, NW, false, true>(a);
+      hipLaunchKernelGGL((rollout_kernel<DT, ROWS, NW, false, true>), dim3(nblk), dim3(NW * 64), lds, s, a);
+    } else {
+      const size_t lds = launch_lds<DT, ROWS, NW, false>(a);
+      hipLaunchKernelGGL((rollout_kernel<DT, ROWS, NW, false, false>), dim3(nblk), dim3(NW * 64), lds, s, a);
+    }
     HIP_CHECK_LAUNCH();
+    return;
+  }
+  if (a.x_fin != nullptr) {   // (the binding refuses it first: the final rows take fixed statistics)
+    dppo_note_error(hipErrorInvalidValue, __FILE__, __LINE__);
     return;
   }
   const size_t lds = launch_lds<DT, ROWS, NW, true>(a);
@@ -548,7 +612,7 @@ void launch(const RolloutArgs& a, hipStream_t s) {
   }
   RolloutArgs aa = a;
   void* args[] = {&aa};
-  e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true>), dim3(nblk),
+  e = hipLaunchCooperativeKernel(reinterpret_cast<const void*>(rollout_kernel<DT, ROWS, NW, true, false>), dim3(nblk),
                                  dim3(NW * 64), args, (unsigned)lds, s);
   if (e != hipSuccess) dppo_note_error(e, __FILE__, __LINE__);
 }

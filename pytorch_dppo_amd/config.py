@@ -70,6 +70,11 @@ class Params:
     obs_norm_update: str = "rollout"     # step (model.py:68 per step) | rollout (one merge per rollout)
     reward_clip: float = 1.0             # train.py:96 clips to +-1; <=0 disables
     normalize_adv: bool = False
+    bootstrap_time_limit: bool = False   # an episode ended by the step limit alone (truncated, not terminal) is
+                                         # bootstrapped with V of the observation the env reached before its reset:
+                                         # delta_t = r_t + gamma * V(s_{t+1}^true) - V_t, recursion still cut.  False: the
+                                         # reference's GAE, which zeroes V_{t+1} at every episode end (train.py:98-112).
+                                         # Refused with obs_norm_update=step, compat and env_backend=gym.
     minibatches_per_epoch: int = 0       # 0 = buffer // batch_size (full pass); reference ppo.py uses 1
     total_env_steps: int = 0             # 0 = unbounded (use max_iters)
     max_iters: int = 0                   # 0 = unbounded
@@ -168,6 +173,16 @@ class Params:
             self.std_convention = "var"
         if self.obs_norm_update not in ("step", "rollout"):
             raise ValueError("obs_norm_update must be step|rollout")
+        if self.bootstrap_time_limit:
+            if self.obs_norm_update == "step":
+                raise ValueError("bootstrap_time_limit is not built for obs_norm_update=step (the per-step filter's "
+                                 "launches); use obs_norm_update=rollout")
+            if self.compat:
+                raise ValueError("bootstrap_time_limit cannot be combined with compat: compat reproduces the "
+                                 "reference, which zeroes the value at every episode end")
+            if self.env_backend == "gym":
+                raise ValueError("bootstrap_time_limit needs the final observation of a truncated step; "
+                                 "env_backend=gym auto-resets on the host and does not keep it")
         if self.eval_mode not in ("process", "inline"):
             raise ValueError(f"eval_mode must be process|inline, got {self.eval_mode}")
         if int(self.eval_envs) < 1:

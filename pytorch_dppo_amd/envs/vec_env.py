@@ -58,6 +58,9 @@ class VecEnv:
         self.state = torch.zeros(self.E, self.state_dim, device=self.device, dtype=torch.float32)
         self.ep_len = torch.zeros(self.E, device=self.device, dtype=torch.int32)
         self.ep_ret = torch.zeros(self.E, device=self.device, dtype=torch.float32)
+        # bootstrap_time_limit: step() also reports which envs ended by the step limit alone and the
+        # observation each env reached before the in-place reset (info "truncated" / "final_obs")
+        self.report_final = False
 
     # -- subclass API ----------------------------------------------------------------------
     @property
@@ -92,12 +95,17 @@ class VecEnv:
         finished_ret = torch.where(done, self.ep_ret, torch.zeros_like(self.ep_ret))
         finished_len = torch.where(done, self.ep_len, torch.zeros_like(self.ep_len))
         reset_state = self._reset_state(k)
+        extra = {}
+        if self.report_final:
+            # terminal wins when both hold; the final observation is observe() of the stepped state
+            self.state = new_state
+            extra = {"truncated": done & ~terminal, "final_obs": self.observe()}
         self.state = torch.where(done[:, None], reset_state, new_state)
         self.ep_len = torch.where(done, torch.zeros_like(self.ep_len), self.ep_len)
         self.ep_ret = torch.where(done, torch.zeros_like(self.ep_ret), self.ep_ret)
         self.t += 1
         info = {"ep_return_sum": finished_ret.sum(), "ep_count": done.sum(),
-                "finished_ret": finished_ret, "finished_len": finished_len}
+                "finished_ret": finished_ret, "finished_len": finished_len, **extra}
         return self.observe(), reward, done, info
 
     def kernel_params(self) -> Dict:

@@ -6,7 +6,7 @@ tested against these at fp32 (tight) and bf16/fp8 (loose) tolerances.
 from __future__ import annotations
 
 import math
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -64,7 +64,7 @@ def normal_pdf_var(x: torch.Tensor, mu: torch.Tensor, var: torch.Tensor) -> torc
 
 
 def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, gamma: float,
-        lam: float, segment: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        lam: float, segment: int = 0, boot: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """GAE(lambda) over a [T,E] rollout (train.py:109-122, ppo.py:119-133, vectorised).
 
     ``values`` is [T+1,E] (row T = bootstrap V(s_T)); ``dones[t]`` = episode ended at step t
@@ -74,6 +74,10 @@ def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, gamma:
     restarts after a done).  Where a segment ends by length without a done the recursion
     restarts (A_{t+1} masked) while the bootstrap V_{t+1} of the not-done state is kept
     (train.py:109-112 per segment).
+    ``boot`` [T,E] (``bootstrap_time_limit``): the value of the observation a step-limit ("truncated")
+    episode end reached before its reset, 0 elsewhere.  It enters ``delta`` only,
+    ``delta_t = r_t + gamma * (V_{t+1} * (1 - d_t) + boot_t) - V_t``; the recursion stays cut at the done.
+    ``None`` is the function without it, bit for bit.
     Returns (advantages [T,E], returns [T,E]) with returns = A + V.
     """
     T = rewards.shape[0]
@@ -90,7 +94,10 @@ def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, gamma:
     nxt = torch.zeros_like(rewards[0])
     for t in range(T - 1, -1, -1):
         nonterm = 1.0 - dones[t].to(rewards.dtype)
-        delta = rewards[t] + gamma * values[t + 1] * nonterm - values[t]
+        if boot is None:
+            delta = rewards[t] + gamma * values[t + 1] * nonterm - values[t]
+        else:
+            delta = rewards[t] + gamma * (values[t + 1] * nonterm + boot[t]) - values[t]
         nxt = delta + gamma * lam * nonterm * cont[t] * nxt
         adv[t] = nxt
     return adv, adv + values[:T]

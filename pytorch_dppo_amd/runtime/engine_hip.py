@@ -362,6 +362,22 @@ class HipEngine:
         elif bool(getattr(params, "env_fused", False)):
             self.kernel_kind = kernel_kind_of(env)
         self.stepped_env = not self.host_env and self.kernel_kind is None
+        # bootstrap_time_limit: which steps ended by the step limit alone (trunc, like dones), the
+        # normalised observation each reached before its reset (x_fin [K][E][d0] in x_buf's storage:
+        # slot t // limit, an env's truncations being >= limit steps apart) and its value.  Transient:
+        # rewritten by every rollout, never checkpointed.  Allocated only with the flag on.
+        self.boot = bool(getattr(params, "bootstrap_time_limit", False))
+        if self.boot:
+            if self.host_env:
+                raise ValueError("bootstrap_time_limit needs the final observation of a truncated step; a "
+                                 "host-stepped (gym) env auto-resets on the host")
+            self.fin_K = -(-T // int(env.limit))
+            self.trunc = torch.zeros(self.N, **f32)
+            self.x_fin = torch.zeros(self.fin_K * E, self.d0, dtype=self.sdtype, **dev)
+            self.v_fin = torch.zeros(self.fin_K * E, **f32)
+            self.boot_buf = torch.zeros(self.N, **f32)
+            self._fin_rows = torch.zeros(E, self.d0, dtype=self.sdtype, **dev)   # rollout_stepped's scratch rows
+            self._fin_slot = None
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -663,11 +679,15 @@ class HipEngine:
                 kp["limit"], 1 if self.p.std_convention == "var" else 0]
         keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
         xt = xT if xT is not None else self.empty_x
-        self.ext.rollout(self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout,
-                         self.scales, self.model.flat.data, norm.mean_f32, norm.inv_std_f32, shift, self.x_buf,
-                         self.actions, self.logp, self.rewards, self.dones,
-                         self.mom if mom is None else mom, self.epstat if epstat is None else epstat, ints, keys,
-                         float(self.p.reward_clip), self.qscale, xt, self.x_rows[0])
+        args = (self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout,
+                self.scales, self.model.flat.data, norm.mean_f32, norm.inv_std_f32, shift, self.x_buf,
+                self.actions, self.logp, self.rewards, self.dones,
+                self.mom if mom is None else mom, self.epstat if epstat is None else epstat, ints, keys,
+                float(self.p.reward_clip), self.qscale, xt, self.x_rows[0])
+        if self.boot:
+            self.ext.rollout_fin(*args, self.trunc, self.x_fin, self.fin_K)
+        else:
+            self.ext.rollout(*args)
 
     def _kind(self) -> int:
         """the in-kernel env kind of the rollout / eval launches; an env that has none never gets here
@@ -867,10 +887,15 @@ class HipEngine:
           4. ``env.t += 1``, ``obs = env.observe()``
 
         then a rows-only act launch for the bootstrap rows and one obs_reduce.  The update runs on
-        the usual kernels; the return dict is the other paths'."""
+        the usual kernels; the return dict is the other paths'.  With ``bootstrap_time_limit`` step 3
+        is preceded by ``observe()`` of the new state and a rows-only act launch into scratch rows,
+        and ``env_advance_fin`` also writes the step's ``trunc`` row and copies the truncated envs'
+        scratch rows into the slot ``x_fin[t // limit]``; still no host sync."""
         if self.host_env:
             raise RuntimeError("rollout_stepped() steps a builtin tensor env on the device; a host-stepped (gym) env "
                                "takes rollout()")
+        if self.boot and self.p.obs_norm_update == "step":
+            raise ValueError("bootstrap_time_limit is not built for obs_norm_update=step")
         self._flush_value()        # (fp8: the refresh reads every layer; and the reduce rewrites ep_sum)
         self.refresh_fwd_image()
         p, T, E, O, env = self.p, self.T, self.E, self.O, self.env
@@ -899,10 +924,24 @@ class HipEngine:
             new_state, reward, terminal = env._dynamics(a, k)
             reset_state = env._reset_state(k)
             # (.to / .contiguous: no-ops for an env that returns fp32 / bool contiguous tensors)
-            self.ext.env_advance(reward.to(torch.float32).contiguous(), terminal.to(torch.bool).contiguous(),
-                                 new_state.to(torch.float32).contiguous(), reset_state.to(torch.float32).contiguous(),
-                                 env.state, env.ep_len, env.ep_ret, self.rewards[rows], self.dones[rows],
-                                 self.epstat, env.limit, clip, t == 0)
+            adv_args = (reward.to(torch.float32).contiguous(), terminal.to(torch.bool).contiguous(),
+                        new_state.to(torch.float32).contiguous(), reset_state.to(torch.float32).contiguous(),
+                        env.state, env.ep_len, env.ep_ret, self.rewards[rows], self.dones[rows],
+                        self.epstat, env.limit, clip, t == 0)
+            if self.boot:
+                # the observation of the stepped state (VecEnv.step's final_obs) as buffer rows: one
+                # rows-only act launch into the scratch rows; env_advance copies the truncated envs'
+                # rows into this step's x_fin slot.  The env's live state tensor is put back at once.
+                live, env.state = env.state, adv_args[2]
+                fobs = env.observe().to(torch.float32).contiguous()
+                env.state = live
+                self._launch_act(fobs, k, False, 0, self.key_action, norm, shift, none, none, none, self._fin_rows,
+                                 none, False)
+                slot = t // env.limit
+                self.ext.env_advance_fin(*adv_args, self._fin_rows, self.x_fin[slot * E:(slot + 1) * E],
+                                         self.trunc[rows])
+            else:
+                self.ext.env_advance(*adv_args)
             env.t += 1
             obs = env.observe().to(torch.float32).contiguous()
         # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
@@ -1135,13 +1174,32 @@ class HipEngine:
             self.ext.mlp_value(self.dt_fwd, self.x_raw, self.empty, 0, self.E, self.wimg_fwd, self.layout,
                                self.scales, self.model.flat.data, self.A, self.values_buf[self.N:], False,
                                self.qscale, self.no_u8)
+        if self.boot:
+            # V of the final rows: the same forward over x_fin's K * E rows (rows never written are
+            # zero rows: a finite value that gae() masks)
+            Mf = self.fin_K * self.E
+            if self.fp8 and self.heads:
+                self.ext.mlp_value(self.dt, self.x_fin, self.empty, 0, Mf, self.wimg, self.layout, self.scales,
+                                   self.model.flat.data, self.A, self.v_fin, False, self.qscale, self.wimg_fwd)
+            else:
+                self.ext.mlp_value(self.dt_fwd, self.x_fin, self.empty, 0, Mf, self.wimg_fwd, self.layout, self.scales,
+                                   self.model.flat.data, self.A, self.v_fin, False, self.qscale, self.no_u8)
 
     @torch.no_grad()
     def gae(self) -> None:
         T, E = self.T, self.E
-        self.ext.gae(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
-                     self.adv.view(T, E), self.ret.view(T, E), float(self.p.gamma), float(self.p.gae_param), 0,
-                     self.p.gae_segment())
+        if self.boot:
+            # boot[t, e] = trunc[t, e] ? v_fin[t // limit, e] : 0
+            if self._fin_slot is None:
+                self._fin_slot = torch.arange(T, device=self.device) // int(self.env.limit)
+            torch.mul(self.trunc.view(T, E), self.v_fin.view(self.fin_K, E)[self._fin_slot], out=self.boot_buf.view(T, E))
+            self.ext.gae_boot(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
+                              self.boot_buf.view(T, E), self.adv.view(T, E), self.ret.view(T, E), float(self.p.gamma),
+                              float(self.p.gae_param), 0, self.p.gae_segment())
+        else:
+            self.ext.gae(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
+                         self.adv.view(T, E), self.ret.view(T, E), float(self.p.gamma), float(self.p.gae_param), 0,
+                         self.p.gae_segment())
         if self.p.normalize_adv:
             m, s = self.adv.mean(), self.adv.std()
             self.adv.sub_(m).div_(s + 1e-8)

@@ -47,6 +47,16 @@ class TorchEngine:
         self.dones = torch.zeros(T, E, **f32)
         self.adv = torch.zeros(T, E, **f32)
         self.ret = torch.zeros(T, E, **f32)
+        # bootstrap_time_limit: which steps ended by the step limit alone, the normalised observation
+        # each reached before its reset (slot t // limit: an env's truncations are >= limit steps
+        # apart) and its value
+        self.boot = bool(params.bootstrap_time_limit)
+        if self.boot:
+            env.report_final = True
+            self.fin_K = -(-T // env.limit)
+            self.trunc = torch.zeros(T, E, **f32)
+            self.x_fin = torch.zeros(self.fin_K, E, O, **f32)
+            self.v_fin = torch.zeros(self.fin_K, E, **f32)
         n = model.num_params
         self.grad_flat = torch.zeros(n, **f32)
         self.adam_m = torch.zeros(n, **f32)
@@ -98,6 +108,11 @@ class TorchEngine:
             self.logp[t] = logp
             self.rewards[t] = r
             self.dones[t] = done.to(torch.float32)
+            if self.boot:
+                tr = info["truncated"].to(self.device)
+                self.trunc[t] = tr.to(torch.float32)
+                slot = self.x_fin[t // self.env.limit]
+                slot[tr] = norm_stats.normalize(info["final_obs"].to(self.device))[tr]
             ep_ret_sum += info["ep_return_sum"].to(torch.float64)
             ep_count += info["ep_count"].to(torch.float64)
             self.obs = obs.to(self.device)
@@ -114,11 +129,18 @@ class TorchEngine:
         if self.p.compat:  # Q8: bootstrap with the raw, un-normalised state (train.py:111)
             _, _, vb = self.model(self.raw_last)
             self.values_buf[T] = vb.reshape(E)
+        if self.boot:
+            _, _, vf = self.model(self.x_fin.reshape(self.fin_K * E, self.O))
+            self.v_fin.copy_(vf.reshape(self.fin_K, E))
 
     @torch.no_grad()
     def gae(self) -> None:
+        boot = None
+        if self.boot:
+            slot = torch.arange(self.T, device=self.device) // self.env.limit
+            boot = self.trunc * self.v_fin[slot]
         adv, ret = oracle.gae(self.rewards, self.values_buf, self.dones, self.p.gamma, self.p.gae_param,
-                              segment=self.p.gae_segment())
+                              segment=self.p.gae_segment(), boot=boot)
         if self.p.normalize_adv:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         self.adv.copy_(adv)
