@@ -921,6 +921,59 @@ void gae_boot(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, 
   after_launch(__func__);
 }
 
+// gae_boot() on the reward r' = clamp(fl32(r * scale[0]), +-rclip) (reward_norm; rclip <= 0: no clamp): scale
+// is a device scalar, read by the kernel
+void gae_rn(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor scale,
+            double rclip, torch::Tensor adv, torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
+  TORCH_CHECK(seg >= 0, "segment length must be >= 0 (0: no segment cut)");
+  TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "gae mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
+  const int64_t T = rewards.size(0), E = rewards.size(1);
+  check(rewards, "rewards", at::kFloat, T * E);
+  check(values, "values", at::kFloat, (T + 1) * E);
+  check(dones, "dones", at::kFloat, T * E);
+  check(scale, "scale", at::kFloat, 1);
+  check(adv, "adv", at::kFloat, T * E);
+  check(ret, "ret", at::kFloat, T * E);
+  const float* b = nullptr;
+  if (boot.defined() && boot.numel() > 0) {
+    check(boot, "boot", at::kFloat, T * E);
+    b = boot.data_ptr<float>();
+  }
+  launch_gae_rn(rewards.data_ptr<float>(), values.data_ptr<float>(), dones.data_ptr<float>(), b,
+                scale.data_ptr<float>(), (float)rclip, adv.data_ptr<float>(), ret.data_ptr<float>(), (int)T, (int)E,
+                (float)gamma, (float)lam, (int)mode, (int)seg, cur_stream());
+  after_launch(__func__);
+}
+
+// reward_norm: the discounted-return scan of a rollout (csrc/retnorm.hip).  ret_acc [E] is updated in place,
+// s12 [2] fp64 = (S1, S2) of the T*E samples about shift[0]; R_out [T,E] is optional (an empty tensor: not
+// written); part: fp64 scratch of ret_scan_nblk(T, E, mode) x 2
+int64_t ret_scan_nblk(int64_t T, int64_t E, int64_t mode) { return ret_scan_blocks((int)T, (int)E, (int)mode); }
+
+void ret_scan(torch::Tensor rewards, torch::Tensor dones, torch::Tensor ret_acc, torch::Tensor shift,
+              torch::Tensor part, torch::Tensor s12, torch::Tensor R_out, double gamma, int64_t mode) {
+  TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "ret_scan mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
+  const int64_t T = rewards.size(0), E = rewards.size(1);
+  TORCH_CHECK(T > 0 && E > 0, "rewards must not be empty");
+  check(rewards, "rewards", at::kFloat, T * E);
+  check(dones, "dones", at::kFloat, T * E);
+  check(ret_acc, "ret_acc", at::kFloat, E);
+  check(shift, "shift", at::kFloat, 1);
+  check(part, "part", at::kDouble, 2 * ret_scan_nblk(T, E, mode));
+  check(s12, "s12", at::kDouble, 2);
+  float* ro = nullptr;
+  if (R_out.defined() && R_out.numel() > 0) {
+    check(R_out, "R_out", at::kFloat, T * E);
+    ro = R_out.data_ptr<float>();
+  }
+  launch_ret_scan(rewards.data_ptr<float>(), dones.data_ptr<float>(), ret_acc.data_ptr<float>(),
+                  shift.data_ptr<float>(), ro, part.data_ptr<double>(), s12.data_ptr<double>(), (int)T, (int)E,
+                  (float)gamma, (int)mode, cur_stream());
+  after_launch(__func__);
+}
+
 void metrics_pack(torch::Tensor ep, torch::Tensor loss8, torch::Tensor norm_part, torch::Tensor out) {
   check(ep, "ep", at::kDouble, 2);
   check(loss8, "loss8", at::kFloat, 8);
@@ -1109,6 +1162,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_gather", &grad_gather);
   m.def("gae", &gae);
   m.def("gae_boot", &gae_boot);
+  m.def("gae_rn", &gae_rn);
+  m.def("ret_scan", &ret_scan);
+  m.def("ret_scan_nblk", &ret_scan_nblk);
   m.def("set_adam_fused", [](int64_t on) { set_adam_fused((int)on); });
   m.def("obs_reduce", &obs_reduce);
   m.def("obs_merge", &obs_merge);

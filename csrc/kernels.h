@@ -325,6 +325,17 @@ void launch_gae(const float* rewards, const float* values, const float* dones, f
 // boot: optional [T][E] value of a truncated step's final observation (null: launch_gae)
 void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot, float* adv,
                      float* ret, int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s);
+// scale: optional device scalar (reward_norm: r' = clamp(fl32(r * scale), +-rclip), rclip <= 0: no clamp;
+// null: launch_gae_boot)
+void launch_gae_rn(const float* rewards, const float* values, const float* dones, const float* boot,
+                   const float* scale, float rclip, float* adv, float* ret, int T, int E, float gamma, float lam,
+                   int mode, int seg, hipStream_t s);
+// csrc/retnorm.hip: forward scan of the discounted return over [T][E] rewards / dones (acc [E] in place),
+// s12 = the samples' (S1, S2) about shift[0]; mode as launch_gae_boot; R_out optional [T][E] (null: skipped);
+// part: ret_scan_blocks(T, E, mode) x 2 doubles of scratch
+int ret_scan_blocks(int T, int E, int mode);
+void launch_ret_scan(const float* rewards, const float* dones, float* acc, const float* shift, float* R_out,
+                     double* part, double* s12, int T, int E, float gamma, int mode, hipStream_t s);
 void set_adam_fused(int on);
 void launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                  float eps, float max_norm, float* state, float* norm_part, int nblk,

@@ -23,13 +23,43 @@ DEV bool seg_cut(int t, int td, int seg, float d) { return d == 0.f && (t - td) 
 // BOOT: boot [T][E] (bootstrap_time_limit: V of the observation a step-limit episode end reached
 // before its reset, 0 elsewhere) enters delta only, delta_t = r_t + gamma*(V_{t+1}*(1-d_t) + boot_t) - V_t;
 // the recursion stays cut at the done.  !BOOT is the kernel without it, instruction for instruction.
-template <bool BOOT>
+// RN (reward_norm): the reward enters as r' = clamp(fl32(r * scale), +-rclip) (rclip <= 0: no clamp),
+// scale read from device memory (the return statistics' fp32 1/std image, merged just before on
+// this stream); the product is rounded on its own, so adv / ret carry the bits of the !RN kernel
+// run on a buffer scaled beforehand.  !RN takes an empty argument and is the kernel without it.
+template <bool RN> struct GaeScale { const float* scale; float rclip; };
+template <> struct GaeScale<false> {};
+DEV float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+template <bool RN>
+DEV float gae_reward(float r, float sc, float rclip) {
+  if constexpr (RN) {
+    r = mul_rn(r, sc);
+    if (rclip > 0.f) r = fminf(fmaxf(r, -rclip), rclip);
+  }
+  return r;
+}
+template <bool RN>
+DEV float gae_scale(const GaeScale<RN>& rn, float& rclip) {
+  if constexpr (RN) {
+    rclip = rn.rclip;
+    return *rn.scale;
+  } else {
+    rclip = 0.f;
+    return 1.f;
+  }
+}
+template <bool BOOT, bool RN>
 __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, const float* __restrict__ val,
                                                  const float* __restrict__ done, const float* __restrict__ boot,
                                                  float* __restrict__ adv, float* __restrict__ ret, int T, int E,
-                                                 float gamma, float lam, int seg) {
+                                                 float gamma, float lam, int seg, GaeScale<RN> rn) {
   const int e = blockIdx.x * 64 + threadIdx.x;
   if (e >= E) return;
+  float rclip;
+  const float sc = gae_scale<RN>(rn, rclip);
   if (seg > 0) {
     int td = -1;
     for (int t = 0; t < T; ++t) {
@@ -55,7 +85,7 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const size_t o = (size_t)(t - k) * E + e;
-      r[k] = rew[o];
+      r[k] = gae_reward<RN>(rew[o], sc, rclip);
       v[k] = val[o];
       d[k] = done[o];
       c[k] = seg > 0 ? adv[o] : 1.f;
@@ -66,7 +96,7 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
   }
   for (; t >= 0; --t) {
     const size_t o = (size_t)t * E + e;
-    step(o, rew[o], val[o], done[o], seg > 0 ? adv[o] : 1.f, BOOT ? boot[o] : 0.f);
+    step(o, gae_reward<RN>(rew[o], sc, rclip), val[o], done[o], seg > 0 ? adv[o] : 1.f, BOOT ? boot[o] : 0.f);
   }
 }
 
@@ -78,14 +108,16 @@ __global__ __launch_bounds__(64) void gae_kernel(const float* __restrict__ rew, 
 // exclusive scan over the 256 chunk maps (in LDS, Hillis-Steele) gives each chunk its incoming
 // A_{t1}, and every thread replays its chunk to write adv / ret.  Same arithmetic per step as
 // gae_kernel; only the association of the products differs (fp32 rounding-level).
-template <bool BOOT>
+template <bool BOOT, bool RN>
 __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__ rew, const float* __restrict__ val,
                                                        const float* __restrict__ done, const float* __restrict__ boot,
                                                        float* __restrict__ adv, float* __restrict__ ret, int T, int E,
-                                                       float gamma, float lam, int seg) {
+                                                       float gamma, float lam, int seg, GaeScale<RN> rn) {
   __shared__ float sD[256], sC[256];
   __shared__ int sT[256];
   const int e = blockIdx.x, j = threadIdx.x;
+  float rclip;
+  const float sc = gae_scale<RN>(rn, rclip);
   const int chunk = (T + 255) / 256;
   const int t0 = min(T, j * chunk), t1 = min(T, t0 + chunk);
   if (seg > 0) {
@@ -113,8 +145,9 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
   auto delta_c = [&](int t, float& delta, float& c) {
     const size_t o = (size_t)t * E + e;
     const float nt = 1.f - done[o];
-    if constexpr (BOOT) delta = rew[o] + gamma * (val[o + E] * nt + boot[o]) - val[o];
-    else delta = rew[o] + gamma * val[o + E] * nt - val[o];
+    const float r = gae_reward<RN>(rew[o], sc, rclip);
+    if constexpr (BOOT) delta = r + gamma * (val[o + E] * nt + boot[o]) - val[o];
+    else delta = r + gamma * val[o + E] * nt - val[o];
     c = gamma * lam * nt * (seg > 0 ? adv[o] : 1.f);
   };
   float D = 0.f, C = 1.f;
@@ -542,25 +575,43 @@ extern "C" void launch_metrics_pack(const double* ep, const float* loss8, const 
   HIP_CHECK_LAUNCH();
 }
 
-// boot: optional [T][E] (null: the kernels without it)
-extern "C" void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot,
-                                float* adv, float* ret, int T, int E, float gamma, float lam, int mode, int seg,
-                                hipStream_t s) {
+// boot: optional [T][E] (null: the kernels without it); scale: optional device scalar (null: the
+// kernels without the reward scaling; rclip is then unread)
+extern "C" void launch_gae_rn(const float* rewards, const float* values, const float* dones, const float* boot,
+                              const float* scale, float rclip, float* adv, float* ret, int T, int E, float gamma,
+                              float lam, int mode, int seg, hipStream_t s) {
   // mode 0 = auto: the per-env lane scan keeps >= 1 full wave busy per env batch; with few envs
   // and a long horizon its single dependent chain per lane is the latency, so scan in time.
   const bool scan = mode == 2 || (mode == 0 && E <= 64 && T >= 512);
   const dim3 grid = scan ? dim3(E) : dim3((E + 63) / 64), block = scan ? dim3(256) : dim3(64);
-  auto go = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, rewards, values, dones, boot, adv, ret, T, E, gamma, lam, seg);
+  auto go = [&](auto kernel, auto rn) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, rewards, values, dones, boot, adv, ret, T, E, gamma, lam, seg, rn);
   };
-  if (boot != nullptr) {
-    if (scan) go(gae_scan_kernel<true>);
-    else go(gae_kernel<true>);
+  if (scale != nullptr) {
+    const GaeScale<true> rn{scale, rclip};
+    if (boot != nullptr) {
+      if (scan) go(gae_scan_kernel<true, true>, rn);
+      else go(gae_kernel<true, true>, rn);
+    } else {
+      if (scan) go(gae_scan_kernel<false, true>, rn);
+      else go(gae_kernel<false, true>, rn);
+    }
   } else {
-    if (scan) go(gae_scan_kernel<false>);
-    else go(gae_kernel<false>);
+    const GaeScale<false> rn{};
+    if (boot != nullptr) {
+      if (scan) go(gae_scan_kernel<true, false>, rn);
+      else go(gae_kernel<true, false>, rn);
+    } else {
+      if (scan) go(gae_scan_kernel<false, false>, rn);
+      else go(gae_kernel<false, false>, rn);
+    }
   }
   HIP_CHECK_LAUNCH();
+}
+extern "C" void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot,
+                                float* adv, float* ret, int T, int E, float gamma, float lam, int mode, int seg,
+                                hipStream_t s) {
+  launch_gae_rn(rewards, values, dones, boot, nullptr, 0.f, adv, ret, T, E, gamma, lam, mode, seg, s);
 }
 extern "C" void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
                            int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s) {

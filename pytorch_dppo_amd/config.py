@@ -75,6 +75,11 @@ class Params:
                                          # delta_t = r_t + gamma * V(s_{t+1}^true) - V_t, recursion still cut.  False: the
                                          # reference's GAE, which zeroes V_{t+1} at every episode end (train.py:98-112).
                                          # Refused with obs_norm_update=step, compat and env_backend=gym.
+    reward_norm: bool = False            # GAE reads r' = r / (running std of the discounted return) (the
+                                         # VecNormalize(norm_reward=True) rule; ops/oracle.return_scan).  The stored
+                                         # rewards, episode returns and evaluation keep raw units.  Use with
+                                         # reward_clip 0.  Refused with compat and with stats_stream on|auto.
+    reward_norm_clip: float = 10.0       # r' clamped to +-this; <=0 disables
     minibatches_per_epoch: int = 0       # 0 = buffer // batch_size (full pass); reference ppo.py uses 1
     total_env_steps: int = 0             # 0 = unbounded (use max_iters)
     max_iters: int = 0                   # 0 = unbounded
@@ -193,6 +198,13 @@ class Params:
                          ("update_kernels", ("auto", "heads", "tile")), ("stats_stream", ("off", "on", "auto"))):
             if getattr(self, name) not in ok:
                 raise ValueError(f"{name} must be {'|'.join(ok)}, got {getattr(self, name)}")
+        if self.reward_norm:
+            if self.compat:
+                raise ValueError("reward_norm cannot be combined with compat: compat reproduces the reference, "
+                                 "whose only reward scaling is the clip to +-1")
+            if self.stats_stream != "off":
+                raise ValueError("reward_norm is not built for stats_stream=on|auto: the return scale is merged on "
+                                 "the compute stream before GAE reads it; use stats_stream=off")
 
     def heartbeat_interval(self, world_size: int) -> float:
         """the heartbeat period in effect: heartbeat_s, or 5 s (auto) whenever there are peers"""

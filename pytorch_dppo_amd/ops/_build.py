@@ -24,7 +24,8 @@ OUT_DIR = os.path.dirname(os.path.abspath(__file__))
 EXT_NAME = "_dppo_hip"
 ARCH = os.environ.get("DPPO_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-DEVICE_SRCS = ["rollout.hip", "eval.hip", "act.hip", "envstep.hip", "mlp.hip", "mlp_head.hip", "phead.hip", "wgrad.hip", "optim.hip", "obs.hip"]
+DEVICE_SRCS = ["rollout.hip", "eval.hip", "act.hip", "envstep.hip", "mlp.hip", "mlp_head.hip", "phead.hip", "wgrad.hip", "optim.hip", "obs.hip",
+               "retnorm.hip"]
 HOST_SRCS = ["bindings.cpp", "comm.cpp"]   # compiled with the torch include paths
 
 
@@ -96,7 +97,9 @@ def build(verbose: bool = False, force: bool = False, variant: str = "", csrc: s
     load_variant) so kernel versions can be timed interleaved in one process on one box."""
     os.makedirs(BUILD, exist_ok=True)
     tcflags, ldflags = _torch_flags(EXT_NAME + (f"_{variant}" if variant else ""))
-    jobs = [(s, []) for s in DEVICE_SRCS] + [(s, tcflags) for s in HOST_SRCS]
+    # (an earlier commit's csrc/ built as a variant may predate a source of this list)
+    dsrcs = [s for s in DEVICE_SRCS if csrc == CSRC or os.path.exists(os.path.join(csrc, s))]
+    jobs = [(s, []) for s in dsrcs] + [(s, tcflags) for s in HOST_SRCS]
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         extra = [f"-D{d}" for d in defines]
         objs = list(ex.map(lambda j: _compile(j[0], j[1], verbose, csrc, extra), jobs))

@@ -103,6 +103,39 @@ def gae(rewards: torch.Tensor, values: torch.Tensor, dones: torch.Tensor, gamma:
     return adv, adv + values[:T]
 
 
+def return_scan(rewards: torch.Tensor, dones: torch.Tensor, gamma: float, acc: torch.Tensor, shift,
+                return_R: bool = False):
+    """Forward scan of the discounted return over a [T,E] rollout (``reward_norm``; the
+    VecNormalize(norm_reward=True) statistic)::
+
+        R = fl32(fl32(gamma32 * R) + r[t]);  the sample R joins the moments;  R = 0 where done[t]
+
+    from the carry ``acc`` [E] fp32 (two separately rounded fp32 operations: a device twin must not
+    contract them into an FMA).  ``shift`` is the fp32 image of the running mean (a float or a
+    1-element tensor).  Only dones reset the scan: ``gae``'s segment does not cut it.
+    Returns ``(acc', S1, S2)`` — the new carry and, as 0-d fp64 tensors, ``sum(R - shift)`` and
+    ``sum((R - shift)^2)`` over the T*E samples — plus the samples ``R`` [T,E] fp32 with ``return_R``."""
+    T = rewards.shape[0]
+    g32 = torch.tensor(float(gamma), dtype=torch.float32, device=rewards.device)
+    sh = float(shift.reshape(-1)[0]) if torch.is_tensor(shift) else float(torch.tensor(shift, dtype=torch.float32))
+    R = acc.to(torch.float32).clone()
+    out = torch.empty_like(rewards, dtype=torch.float32)
+    zero = torch.zeros_like(R)
+    for t in range(T):
+        R = (g32 * R) + rewards[t].to(torch.float32)
+        out[t] = R
+        R = torch.where(dones[t] != 0, zero, R)
+    d = out.to(torch.float64) - sh
+    s1, s2 = d.sum(), (d * d).sum()
+    return (R, s1, s2, out) if return_R else (R, s1, s2)
+
+
+def scale_rewards(rewards: torch.Tensor, scale: torch.Tensor, clip: float) -> torch.Tensor:
+    """``reward_norm``'s reward as GAE reads it: ``fl32(r * scale)`` clamped to +-clip (clip <= 0: not)."""
+    r = rewards * scale.to(rewards.device, torch.float32).reshape(())
+    return r.clamp(-clip, clip) if clip > 0 else r
+
+
 def ppo_loss(mu, log_std, v, actions, logp_old, adv, ret, v_old, *, clip: float,
              ent_coeff: float, value_loss: str = "mse", convention: str = "std") -> Dict[str, torch.Tensor]:
     """Corrected PPO loss (ppo.py:148-167).

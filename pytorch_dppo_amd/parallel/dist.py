@@ -308,21 +308,24 @@ class DistContext:
         count is count * world_size and no device->host read is needed (the hot path).
         ``extra`` (count_uniform only): a small fp64 device tensor summed over ranks in the SAME
         all-reduce and written back in place — the iteration's episode [return sum, count] (R5)
-        ride along with the moments instead of costing a second collective."""
+        ride along with the moments instead of costing a second collective.  A list / tuple of such
+        tensors rides the same way (``reward_norm``'s return moments beside the episode pair)."""
         if not self.collective:
             return count, s1, s2
         O = s1.numel()
         if count_uniform:
+            extras = [] if extra is None else (list(extra) if isinstance(extra, (list, tuple)) else [extra])
             parts = [s1.reshape(-1).to(self.device, torch.float64), s2.reshape(-1).to(self.device, torch.float64)]
-            if extra is not None:
-                parts.append(extra.reshape(-1).to(self.device, torch.float64))
+            parts += [x.reshape(-1).to(self.device, torch.float64) for x in extras]
             buf = torch.cat(parts)
             if self.native is not None:
                 self.native.allreduce_(buf)          # in stream order
             else:
                 dist.all_reduce(buf, op=dist.ReduceOp.SUM)
-            if extra is not None:
-                extra.copy_(buf[2 * O:].view(extra.shape))
+            lo = 2 * O
+            for x in extras:
+                x.copy_(buf[lo:lo + x.numel()].view(x.shape))
+                lo += x.numel()
             return count * self.world_size, buf[:O], buf[O:2 * O]
         assert extra is None, "extra rides only on the count-uniform all-reduce"
         buf = torch.empty(1 + 2 * O, dtype=torch.float64, device=self.device)

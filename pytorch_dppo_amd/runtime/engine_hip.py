@@ -32,6 +32,8 @@ from ..models.actor_critic import ActorCritic, PackedLayout, fm_index
 from ..ops import native, storage
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
+from ..utils.ret_stats import VAR_FLOOR as RET_VAR_FLOOR, RunningReturnStats
+from .engine_torch import load_ret_acc
 
 STORAGE = storage.STORAGE
 NPART_FIXED = 8
@@ -378,6 +380,19 @@ class HipEngine:
             self.boot_buf = torch.zeros(self.N, **f32)
             self._fin_rows = torch.zeros(E, self.d0, dtype=self.sdtype, **dev)   # rollout_stepped's scratch rows
             self._fin_slot = None
+        # reward_norm: the carry of the discounted-return scan (per rank, checkpointed with the env),
+        # the running statistics of the return (global; merged by csrc/obs.hip obs_merge with O = 1),
+        # the scan's (S1, S2) and per-workgroup scratch (csrc/retnorm.hip), and one more slot of the
+        # metrics vector (return_std).  Allocated only with the flag on.
+        self.ret_stats: Optional[RunningReturnStats] = None
+        self.ret_acc: Optional[torch.Tensor] = None
+        if bool(getattr(params, "reward_norm", False)):
+            self.ret_stats = RunningReturnStats(device)
+            self.ret_stats.device_merge = self._ret_device_merge
+            self.ret_acc = torch.zeros(E, **f32)
+            self.ret_s12 = torch.zeros(2, dtype=torch.float64, **dev)
+            self.ret_part = torch.zeros(2 * int(self.ext.ret_scan_nblk(T, E, 0)), dtype=torch.float64, **dev)
+            self.metrics_buf = torch.zeros(2 + NPART_FIXED + 2, dtype=torch.float64, **dev)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -659,10 +674,40 @@ class HipEngine:
         self.ext.obs_merge(s12, count, n_a, shift.contiguous(), st.mean, st.mean_diff, st.mean_f32,
                            st.inv_std_f32, 1e-2)
 
+    def _ret_device_merge(self, s1, s2, count, n_a, shift) -> None:
+        """RunningReturnStats merge on the device: obs_merge with O = 1 and the return floor (the
+        shift is the statistics' own fp32 mean image, which the kernel reads before it writes)."""
+        rs = self.ret_stats
+        if s1.data_ptr() == self.ret_s12.data_ptr() and s2.data_ptr() == self.ret_s12[1:].data_ptr():
+            s12 = self.ret_s12
+        else:
+            s12 = torch.cat([s1.reshape(1), s2.reshape(1)]).to(torch.float64)
+        self.ext.obs_merge(s12, count, n_a, shift.contiguous(), rs.mean, rs.mean_diff, rs.mean_f32, rs.inv_std_f32,
+                           RET_VAR_FLOOR)
+
+    @torch.no_grad()
+    def return_moments(self) -> torch.Tensor:
+        """reward_norm, after a rollout: the discounted-return scan over the rollout's rewards / dones
+        (csrc/retnorm.hip; ``ret_acc`` advanced in place) -> device fp64 [2] = (S1, S2) of its T*E
+        samples about the statistics' shift.  No host sync; the worker sums it over ranks with the
+        observation moments and hands it to ``merge_return_moments``."""
+        T, E = self.T, self.E
+        self.ext.ret_scan(self.rewards.view(T, E), self.dones.view(T, E), self.ret_acc, self.ret_stats.shift(),
+                          self.ret_part, self.ret_s12, self.no_q, float(self.p.gamma), 0)
+        return self.ret_s12
+
+    def merge_return_moments(self, count: float, s12: torch.Tensor) -> None:
+        rs = self.ret_stats
+        rs.merge_moments(float(count), s12[0:1], s12[1:2], rs.shift())
+
     def env_state(self) -> Dict:
-        return self.env.state_dict()
+        d = self.env.state_dict()
+        if self.ret_acc is not None:
+            d = dict(d, ret_acc=self.ret_acc.detach().cpu().clone())
+        return d
 
     def load_env_state(self, d: Dict) -> None:
+        d = load_ret_acc(self, d)
         self.env.load_state_dict(d)
         if self.host_env:
             # the host envs were restored (and reset): the next rollout acts on their observation,
@@ -1193,6 +1238,13 @@ class HipEngine:
             if self._fin_slot is None:
                 self._fin_slot = torch.arange(T, device=self.device) // int(self.env.limit)
             torch.mul(self.trunc.view(T, E), self.v_fin.view(self.fin_K, E)[self._fin_slot], out=self.boot_buf.view(T, E))
+        if self.ret_stats is not None:
+            # reward_norm: the kernels scale the reward by the device-resident 1/std (boot is a value: not scaled)
+            self.ext.gae_rn(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
+                            self.boot_buf.view(T, E) if self.boot else self.no_q, self.ret_stats.scale,
+                            float(self.p.reward_norm_clip), self.adv.view(T, E), self.ret.view(T, E),
+                            float(self.p.gamma), float(self.p.gae_param), 0, self.p.gae_segment())
+        elif self.boot:
             self.ext.gae_boot(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
                               self.boot_buf.view(T, E), self.adv.view(T, E), self.ret.view(T, E), float(self.p.gamma),
                               float(self.p.gae_param), 0, self.p.gae_segment())
@@ -1568,6 +1620,10 @@ class HipEngine:
             side.wait_stream(torch.cuda.current_stream(self.device))
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             self.ext.metrics_pack(ep2, self._loss_dev, self.norm_part[:n], self.metrics_buf)
+            if self.ret_stats is not None:      # return_std = sqrt(M2 / n) rides in the last slot
+                tail = self.metrics_buf[-1:]
+                torch.mul(self.ret_stats.mean_diff, 1.0 / max(self.ret_stats.n, 1.0), out=tail)
+                tail.sqrt_()
         return self.metrics_buf
 
     def loss_vector(self) -> Optional[torch.Tensor]:

@@ -13,6 +13,7 @@ gae = ``train.py:117-122``; grad = ``train.py:140-166``; apply = ``chief.py:15-1
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Dict, Optional
 
 import torch
@@ -22,6 +23,7 @@ from ..models.actor_critic import ActorCritic
 from ..ops import oracle
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
+from ..utils.ret_stats import RunningReturnStats
 
 
 class TorchEngine:
@@ -57,6 +59,13 @@ class TorchEngine:
             self.trunc = torch.zeros(T, E, **f32)
             self.x_fin = torch.zeros(self.fin_K, E, O, **f32)
             self.v_fin = torch.zeros(self.fin_K, E, **f32)
+        # reward_norm: the carry of the discounted-return scan (per rank, checkpointed with the env) and
+        # the running statistics of the return (global); allocated only with the flag on
+        self.ret_stats: Optional[RunningReturnStats] = None
+        self.ret_acc: Optional[torch.Tensor] = None
+        if bool(params.reward_norm):
+            self.ret_stats = RunningReturnStats(device)
+            self.ret_acc = torch.zeros(E, **f32)
         n = model.num_params
         self.grad_flat = torch.zeros(n, **f32)
         self.adam_m = torch.zeros(n, **f32)
@@ -134,12 +143,28 @@ class TorchEngine:
             self.v_fin.copy_(vf.reshape(self.fin_K, E))
 
     @torch.no_grad()
+    def return_moments(self) -> torch.Tensor:
+        """reward_norm, after a rollout: the discounted-return scan over the rollout's rewards / dones
+        (``ret_acc`` advanced) -> fp64 [2] = (S1, S2) of its T*E samples about the statistics' shift;
+        the worker sums it over ranks and hands it to ``merge_return_moments``."""
+        acc, s1, s2 = oracle.return_scan(self.rewards, self.dones, self.p.gamma, self.ret_acc, self.ret_stats.shift())
+        self.ret_acc.copy_(acc)
+        return torch.stack([s1, s2])
+
+    def merge_return_moments(self, count: float, s12: torch.Tensor) -> None:
+        rs = self.ret_stats
+        rs.merge_moments(float(count), s12[0:1], s12[1:2], rs.shift())
+
+    @torch.no_grad()
     def gae(self) -> None:
         boot = None
         if self.boot:
             slot = torch.arange(self.T, device=self.device) // self.env.limit
             boot = self.trunc * self.v_fin[slot]
-        adv, ret = oracle.gae(self.rewards, self.values_buf, self.dones, self.p.gamma, self.p.gae_param,
+        rewards = self.rewards
+        if self.ret_stats is not None:
+            rewards = oracle.scale_rewards(rewards, self.ret_stats.scale, float(self.p.reward_norm_clip))
+        adv, ret = oracle.gae(rewards, self.values_buf, self.dones, self.p.gamma, self.p.gae_param,
                               segment=self.p.gae_segment(), boot=boot)
         if self.p.normalize_adv:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
@@ -162,9 +187,13 @@ class TorchEngine:
                               p.std_convention, deterministic)
 
     def env_state(self) -> Dict:
-        return self.env.state_dict()
+        d = self.env.state_dict()
+        if self.ret_acc is not None:
+            d = dict(d, ret_acc=self.ret_acc.detach().cpu().clone())
+        return d
 
     def load_env_state(self, d: Dict) -> None:
+        d = load_ret_acc(self, d)
         self.env.load_state_dict(d)
         self.obs = self.env.observe().to(self.device)
 
@@ -224,6 +253,22 @@ class TorchEngine:
 
     def sync(self) -> None:
         pass
+
+
+def load_ret_acc(engine, d: Dict) -> Dict:
+    """the env state without the ``ret_acc`` entry (reward_norm's per-rank carry), which goes into
+    the engine; an env state without one, loaded with the flag on, starts the carry at 0 and warns"""
+    if "ret_acc" not in d:
+        if engine.ret_acc is not None:
+            warnings.warn("reward_norm: the env state has no ret_acc; the return scan starts from 0", UserWarning,
+                          stacklevel=3)
+            engine.ret_acc.zero_()
+        return d
+    d = dict(d)
+    acc = d.pop("ret_acc")
+    if engine.ret_acc is not None:
+        engine.ret_acc.copy_(acc.to(engine.ret_acc.device, torch.float32))
+    return d
 
 
 def _forward_with(model: ActorCritic, flat: torch.Tensor, x: torch.Tensor):

@@ -21,6 +21,7 @@ import math
 import os
 import sys
 import time
+import warnings
 from typing import Dict, Optional
 
 import torch
@@ -158,6 +159,11 @@ class DPPOWorker:
         ep2 = ro.get("ep2")
         ep_extra = ep2 if (torch.is_tensor(ep2) and ep2.dtype == torch.float64 and ep2.device == self.device) else None
         ro["ep2_reduced"] = ep_extra is not None
+        # reward_norm: the return scan's (S1, S2) join the same all-reduce (stats_stream is off: refused
+        # otherwise), then are merged on this stream, ahead of gae()
+        rs12 = eng.return_moments() if p.reward_norm else None
+        if rs12 is not None:
+            ep_extra = [rs12] if ep_extra is None else [ep_extra, rs12]
         if side is not None:
             # rollout-mode stats feed only the NEXT rollout's normalisation: the reduce, the RCCL
             # all-reduce and the Chan merge run on a side stream, overlapping values/GAE/update
@@ -169,6 +175,8 @@ class DPPOWorker:
             self._merge_stats(ro["count"], ro["s1"], ro["s2"], ro["shift"], count_uniform=True, extra=ep_extra)
         if p.obs_norm_update == "step" and hasattr(eng, "after_stats_merge"):
             eng.after_stats_merge()
+        if rs12 is not None:
+            eng.merge_return_moments(float(eng.T * eng.E * (self.ctx.world_size if self.ctx.collective else 1)), rs12)
         tm.stop("obs_stats")
         tm.start("values_gae")
         eng.values()
@@ -264,6 +272,8 @@ class DPPOWorker:
             loss_dev = flat
         else:
             flat, loss_dev = self._stage_parts(ro)
+            if self.p.reward_norm:     # return_std rides in the last slot (pack_metrics wrote its own)
+                flat = torch.cat([flat, eng.ret_stats.std().to(flat.device)])
         if dev.type == "cuda":
             # the stream the metrics were packed on (the side stream while the overlapped value
             # step runs there)
@@ -298,6 +308,7 @@ class DPPOWorker:
         if hasattr(self.engine, "raise_if_failed"):
             self.engine.raise_if_failed()        # (a timed-out per-step filter launch: never report it)
         v = st["host"].tolist()
+        ret_std = v.pop() if p.reward_norm else None
         ep_ret, ep_cnt = v[0], v[1]
         if st["has_loss"]:
             losses = self.engine.losses_from_vector(v[2:])
@@ -311,6 +322,8 @@ class DPPOWorker:
              "iter_s": dt, "steps_per_s": st["steps_local"] * self.ctx.world_size / max(dt, 1e-9),
              "ep_count": ep_cnt, "mean_ep_return": (ep_ret / ep_cnt) if ep_cnt > 0 else float("nan"),
              "grad_norm": gnorm, **losses, **phases}
+        if ret_std is not None:
+            m["return_std"] = ret_std
         if p.verify_sync_every and st["iteration"] % p.verify_sync_every == 0:
             self.quiesce()                       # the checksum reads the value head too
             m["replicas_in_sync"] = self.ctx.verify_replicas(self.model.flat.data)
@@ -417,6 +430,9 @@ class DPPOWorker:
                 "adam_step": eng.adam_step, "obs_stats": self.stats.state_dict(),
                 "iteration": self.iteration, "env_steps": self.env_steps, "updates": self.updates,
                 "config": self.p.to_dict(), "world_size": self.ctx.world_size,
+                # reward_norm: the running (n, mean, M2) of the discounted return (the per-rank carry
+                # ret_acc travels with the env state)
+                **({"ret_stats": eng.ret_stats.state_dict()} if self.p.reward_norm else {}),
                 # fp8 mode's e4m3 wgrad operands: the gradient-maxima ring the next step's delayed
                 # scales come from (a resumed run continues bit-identically)
                 **({"q8_amax": eng.q8_amax.detach().cpu(), "q8_next": eng._q8_next}
@@ -432,6 +448,12 @@ class DPPOWorker:
         self.env_steps = int(st["env_steps"])
         self.updates = int(st["updates"])
         self._stats_initialised = True
+        if self.p.reward_norm:
+            if "ret_stats" in st:
+                eng.ret_stats.load_state_dict(st["ret_stats"])
+            else:
+                warnings.warn("reward_norm: the checkpoint has no return statistics; they start empty", UserWarning,
+                              stacklevel=2)
         if getattr(eng, "q8", False) and "q8_amax" in st:
             eng.q8_amax.copy_(st["q8_amax"].to(eng.q8_amax.device))
             eng._q8_next = int(st["q8_next"])

@@ -3,9 +3,10 @@
 * ``model.pt``          — pure fp32 ``state_dict`` with the reference keys/shapes
                           (``model.py``); loads into the reference ``Model`` with strict=True.
 * ``trainer_state.pt``  — Adam moments + step, obs stats (reference names ``n, mean,
-                          mean_diff, var``, ``model.py:63-66``), counters, config.
+                          mean_diff, var``, ``model.py:63-66``), counters, config; with
+                          ``reward_norm`` the return statistics ``ret_stats`` = ``(n, mean, M2)``.
 * ``env_rank{r}.pt``    — each rank's vectorised env state (so a resumed run continues the
-                          same trajectories).
+                          same trajectories); with ``reward_norm`` the return scan's carry ``ret_acc``.
 Everything is plain tensors / python scalars, loadable with ``weights_only=True``.
 Writes are atomic (tmp + rename) and done by rank 0 (env files by their rank).
 """
