@@ -1008,10 +1008,19 @@ F8Shadow f8_shadow(torch::Tensor img, torch::Tensor lid, torch::Tensor qs, int64
   return f;
 }
 
-void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
-          double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
-          torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, int64_t host_step,
-          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
+// target_kl's gate f32[4] = [stop, applied, trip_kl, last_kl] (csrc/optim.hip KlGate)
+const float* gate_ptr(const torch::Tensor& gate) {
+  check(gate, "gate", at::kFloat, 4);
+  TORCH_CHECK(gate.numel() == 4, "gate is [stop, applied, trip_kl, last_kl]");
+  return gate.data_ptr<float>();
+}
+
+// gate == nullptr: the ungated launch (host_step as below); else the gated form (the step number is
+// state[0] + 1 on the device, host_step unused)
+using CT = const torch::Tensor&;
+void adam_impl(const char* fn, CT p, CT g, CT m, CT v, double lr, double b1, double b2, double eps, double max_norm,
+               CT state, CT norm_part, CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul, int64_t host_step, CT f8_img,
+               CT f8_lid, CT f8_qs, const torch::Tensor* gate) {
   // host_step >= 1: the step number of this update (eager launch: one fused kernel when there is
   // no clipping); 0: read the device counter (graph replay)
   const int64_t n = p.numel();
@@ -1028,22 +1037,56 @@ void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, do
   TORCH_CHECK(nblk >= 1 && nblk <= 4096, "norm_part size");
   const float* q = nullptr;
   if (qmul.defined() && qmul.numel() > 0) { check(qmul, "qmul", at::kFloat, n); q = qmul.data_ptr<float>(); }
-  launch_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr,
-              (float)b1, (float)b2, (float)eps, (float)max_norm, state.data_ptr<float>(), norm_part.data_ptr<float>(),
-              nblk, wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q, (int)host_step,
-              f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
+  if (gate != nullptr)
+    launch_adam_gated(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n,
+                      (float)lr, (float)b1, (float)b2, (float)eps, (float)max_norm, state.data_ptr<float>(),
+                      norm_part.data_ptr<float>(), nblk, wimg.data_ptr(), w_map.data_ptr<int>(),
+                      wt_map.data_ptr<int>(), (int)dt, q, f8_shadow(f8_img, f8_lid, f8_qs, n), gate_ptr(*gate),
+                      cur_stream());
+  else
+    launch_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr,
+                (float)b1, (float)b2, (float)eps, (float)max_norm, state.data_ptr<float>(), norm_part.data_ptr<float>(),
+                nblk, wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q, (int)host_step,
+                f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
+  after_launch(fn);
+}
+
+void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
+          double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
+          torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, int64_t host_step,
+          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
+  adam_impl(__func__, p, g, m, v, lr, b1, b2, eps, max_norm, state, norm_part, wimg, w_map, wt_map, dt, qmul,
+            host_step, f8_img, f8_lid, f8_qs, nullptr);
+}
+
+// target_kl: adam() as a gated step — applied only while gate[0] == 0, step number state[0] + 1 read
+// on the device; one launch without clipping, the sumsq + adam pair with it
+void adam_gated(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
+                double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
+                torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, torch::Tensor f8_img,
+                torch::Tensor f8_lid, torch::Tensor f8_qs, torch::Tensor gate) {
+  adam_impl(__func__, p, g, m, v, lr, b1, b2, eps, max_norm, state, norm_part, wimg, w_map, wt_map, dt, qmul, 0,
+            f8_img, f8_lid, f8_qs, &gate);
+}
+
+// target_kl: the gate after a step (csrc/optim.hip kl_gate_kernel; ops/oracle.py kl_gate)
+void kl_gate(torch::Tensor loss_sums, torch::Tensor gate, torch::Tensor state, double target_kl) {
+  check(loss_sums, "loss_sums", at::kFloat, 8);
+  check(state, "state", at::kFloat, 4);
+  TORCH_CHECK(target_kl > 0, "kl_gate needs target_kl > 0");
+  launch_kl_gate(loss_sums.data_ptr<float>(), const_cast<float*>(gate_ptr(gate)), state.data_ptr<float>(),
+                 (float)target_kl, cur_stream());
   after_launch(__func__);
 }
 
 // grad_gather (reduce items + slab elements of [i_lo, n)) and the no-clip Adam step in one
 // launch (world size 1: nothing runs between them).  Bit-identical parameters to grad_gather ->
 // adam(host_step).  The flat tensors may be one head's slice (red_dst indexes the slice).
-void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
-                 int64_t npblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, std::vector<int64_t> runs,
-                 double scale, torch::Tensor loss_out, torch::Tensor g, torch::Tensor p, torch::Tensor m,
-                 torch::Tensor v, double lr, double b1, double b2, double eps, int64_t step, torch::Tensor state,
-                 torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map, torch::Tensor wt_map, int64_t dt,
-                 torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
+void gather_adam_impl(const char* fn, CT slab, CT src_off, CT src_meta, CT part, int64_t npblk, int64_t npart,
+                      CT red_col, CT red_dst, const std::vector<int64_t>& runs, double scale, CT loss_out, CT g, CT p,
+                      CT m, CT v, double lr, double b1, double b2, double eps, int64_t step, CT state, CT norm_part,
+                      CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul, CT f8_img, CT f8_lid, CT f8_qs,
+                      const torch::Tensor* gate) {
   const int64_t n = p.numel();
   check(p, "p", at::kFloat, n);
   check(g, "g", at::kFloat, n);
@@ -1063,20 +1106,55 @@ void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_me
   check(red_dst, "red_dst", at::kInt, nitems);
   TORCH_CHECK(red_dst.numel() == nitems, "red_col / red_dst");
   const SlabRuns sr = make_runs(runs, n);
-  TORCH_CHECK(step >= 1, "gather_adam needs the host step number (eager launches only)");
+  TORCH_CHECK(gate != nullptr || step >= 1, "gather_adam needs the host step number (eager launches only)");
   const int nblk = (int)norm_part.numel();
   check(norm_part, "norm_part", at::kFloat, nblk);
   TORCH_CHECK(nblk > item_blocks((int)nitems) && nblk <= 4096, "norm_part must hold more blocks than the reduce blocks");
   const float* q = nullptr;
   if (qmul.defined() && qmul.numel() > 0) { check(qmul, "qmul", at::kFloat, n); q = qmul.data_ptr<float>(); }
-  launch_gather_adam(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
-                     part.data_ptr<float>(), (int)npblk, (int)npart, red_col.data_ptr<int>(), red_dst.data_ptr<int>(),
-                     (int)nitems, sr, (float)scale, loss_out.data_ptr<float>(), g.data_ptr<float>(),
-                     p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr, (float)b1,
-                     (float)b2, (float)eps, (int)step, state.data_ptr<float>(), norm_part.data_ptr<float>(), nblk,
-                     wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q,
-                     f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
-  after_launch(__func__);
+  if (gate != nullptr)
+    launch_gather_adam_gated(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
+                             part.data_ptr<float>(), (int)npblk, (int)npart, red_col.data_ptr<int>(),
+                             red_dst.data_ptr<int>(), (int)nitems, sr, (float)scale, loss_out.data_ptr<float>(),
+                             g.data_ptr<float>(), p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n,
+                             (float)lr, (float)b1, (float)b2, (float)eps, state.data_ptr<float>(),
+                             norm_part.data_ptr<float>(), nblk, wimg.data_ptr(), w_map.data_ptr<int>(),
+                             wt_map.data_ptr<int>(), (int)dt, q, f8_shadow(f8_img, f8_lid, f8_qs, n), gate_ptr(*gate),
+                             cur_stream());
+  else
+    launch_gather_adam(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
+                       part.data_ptr<float>(), (int)npblk, (int)npart, red_col.data_ptr<int>(), red_dst.data_ptr<int>(),
+                       (int)nitems, sr, (float)scale, loss_out.data_ptr<float>(), g.data_ptr<float>(),
+                       p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr, (float)b1,
+                       (float)b2, (float)eps, (int)step, state.data_ptr<float>(), norm_part.data_ptr<float>(), nblk,
+                       wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q,
+                       f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
+  after_launch(fn);
+}
+
+void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
+                 int64_t npblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, std::vector<int64_t> runs,
+                 double scale, torch::Tensor loss_out, torch::Tensor g, torch::Tensor p, torch::Tensor m,
+                 torch::Tensor v, double lr, double b1, double b2, double eps, int64_t step, torch::Tensor state,
+                 torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map, torch::Tensor wt_map, int64_t dt,
+                 torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
+  gather_adam_impl(__func__, slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, g,
+                   p, m, v, lr, b1, b2, eps, step, state, norm_part, wimg, w_map, wt_map, dt, qmul, f8_img, f8_lid,
+                   f8_qs, nullptr);
+}
+
+// target_kl: gather_adam() as a gated step (no host step number: state[0] + 1 on the device).  With
+// gate[0] set it still writes g, loss_out and norm_part; p, m, v and the images stay.
+void gather_adam_gated(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
+                       int64_t npblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst,
+                       std::vector<int64_t> runs, double scale, torch::Tensor loss_out, torch::Tensor g,
+                       torch::Tensor p, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2, double eps,
+                       torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map,
+                       torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid,
+                       torch::Tensor f8_qs, torch::Tensor gate) {
+  gather_adam_impl(__func__, slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, g,
+                   p, m, v, lr, b1, b2, eps, 0, state, norm_part, wimg, w_map, wt_map, dt, qmul, f8_img, f8_lid,
+                   f8_qs, &gate);
 }
 
 void fp8_refresh(torch::Tensor p, torch::Tensor lid, torch::Tensor qscale, torch::Tensor part, torch::Tensor wimg,
@@ -1172,6 +1250,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("obs_moments_nblk", &obs_moments_nblk);
   m.def("adam", &adam);
   m.def("gather_adam", &gather_adam);
+  m.def("adam_gated", &adam_gated);
+  m.def("gather_adam_gated", &gather_adam_gated);
+  m.def("kl_gate", &kl_gate);
   m.def("pack", &pack);
   m.def("debug_invalid_launch", &debug_invalid_launch);
   m.def("fp8_refresh", &fp8_refresh);

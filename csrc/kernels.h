@@ -349,6 +349,20 @@ void launch_gather_adam(const float* slab, const int* src_off, const int* src_me
                         int n, float lr, float b1, float b2, float eps, int step, float* state, float* norm_part,
                         int nblk, void* wimg, const int* w_map, const int* wt_map, int dt, const float* img_scale,
                         const F8Shadow& f8, hipStream_t s);
+// target_kl (docs/ARCHITECTURE.md §22): the gated forms of the two launches above — gate f32[4] =
+// [stop, applied, trip_kl, last_kl] is read only, the step number is state[0] + 1 read on the
+// device, and neither writes state[0] / state[1] — and the gate itself (the only writer of both)
+void launch_adam_gated(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                       float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
+                       const int* w_map, const int* wt_map, int dt, const float* img_scale, const F8Shadow& f8,
+                       const float* gate, hipStream_t s);
+void launch_gather_adam_gated(const float* slab, const int* src_off, const int* src_meta, const float* part,
+                              int npblk, int npart, const int* red_col, const int* red_dst, int nitems,
+                              const SlabRuns& runs, float scale, float* loss_out, float* g, float* p, float* m,
+                              float* v, int n, float lr, float b1, float b2, float eps, float* state,
+                              float* norm_part, int nblk, void* wimg, const int* w_map, const int* wt_map, int dt,
+                              const float* img_scale, const F8Shadow& f8, const float* gate, hipStream_t s);
+void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s);
 void launch_pack(const float* p, int n, void* wimg, const int* w_map, const int* wt_map, int dt,
                  const float* img_scale, hipStream_t s);
 // fp8 forward image: qscale[6] = per-layer amax / 416 of p (lid: layer of each parameter, -1

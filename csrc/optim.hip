@@ -184,6 +184,22 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
   }
 }
 
+// target_kl (docs/ARCHITECTURE.md §22): the GATE forms of the Adam launches.  gate f32[4] =
+// [stop, applied, trip_kl, last_kl] and the step counter state[0] are written by kl_gate_kernel
+// alone, in a launch of its own after every step; a GATE launch only reads them, in every
+// workgroup (step number = state[0] + 1), and never writes state[0] / state[1].  With stop set it
+// still does every write that is not p, m, v, a weight image, the e4m3 shadow or the counter (the
+// gradient, the loss sums, the sum-of-squares partials, state[2]).  !GATE takes an empty argument
+// and is the kernel without any of it.
+template <bool GATE> struct KlGate { const float* gate; };
+template <> struct KlGate<false> {};
+template <bool GATE>
+DEV bool kl_stopped(const KlGate<GATE>& kg) {
+  if constexpr (GATE) return kg.gate[0] != 0.f;
+  else return false;
+}
+
+template <bool GATE = false>
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int n, float* __restrict__ part,
                                                     float* __restrict__ state) {
   __shared__ float red[256];
@@ -197,18 +213,20 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   }
   if (threadIdx.x == 0) {
     part[blockIdx.x] = red[0];
-    if (blockIdx.x == 0) state[1] = state[0] + 1.f;  // staged step counter (graph-replay safe)
+    if constexpr (!GATE) {
+      if (blockIdx.x == 0) state[1] = state[0] + 1.f;  // staged step counter (graph-replay safe)
+    }
   }
 }
 
-template <int DT>
+template <int DT, bool GATE = false>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int n, float lr,
                                                    float b1, float b2, float eps, float max_norm,
                                                    float* __restrict__ state, const float* __restrict__ part,
                                                    int nblk, typename Prec<DT>::T* __restrict__ wimg,
                                                    const int* __restrict__ w_map, const int* __restrict__ wt_map,
-                                                   const float* __restrict__ qmul, F8Shadow f8) {
+                                                   const float* __restrict__ qmul, F8Shadow f8, KlGate<GATE> kg) {
   using P = Prec<DT>;
   __shared__ float red[256];
   float s = 0.f;
@@ -222,12 +240,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const float norm = sqrtf(red[0]);
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(1.f, max_norm / (norm + 1e-6f));
-  const float step = state[1];
+  const float step = GATE ? state[0] + 1.f : state[1];
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+  const int i_end = kl_stopped(kg) ? 0 : n;   // (stopped: no element moves)
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < i_end; i += gridDim.x * 256) {
     float mi = m[i], vi = v[i];
     const float pi = adam_elem(mi, vi, p[i], g[i] * coef, b1, b2, step_size, rbc2, eps);
     m[i] = mi;
@@ -243,7 +262,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    state[0] = step;
+    if constexpr (!GATE) state[0] = step;
     state[2] = norm;
   }
 }
@@ -254,16 +273,19 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // iteration for the reported gradient norm.  The step number comes from the host (eager
 // launches); block 0 mirrors it into state[0] for the device-counter path.  Graph replay keeps
 // the sumsq + adam pair, whose step counter lives on the device.
-template <int DT>
+template <int DT, bool GATE = false>
 __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, int n,
-                                                          float lr, float b1, float b2, float eps, float step,
+                                                          float lr, float b1, float b2, float eps, float step_host,
                                                           float* __restrict__ state, float* __restrict__ norm_part,
                                                           typename Prec<DT>::T* __restrict__ wimg,
                                                           const int* __restrict__ w_map,
                                                           const int* __restrict__ wt_map,
-                                                          const float* __restrict__ qmul, F8Shadow f8) {
+                                                          const float* __restrict__ qmul, F8Shadow f8,
+                                                          KlGate<GATE> kg) {
   using P = Prec<DT>;
+  const float step = GATE ? state[0] + 1.f : step_host;
+  const bool stop = kl_stopped(kg);
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1;
@@ -273,6 +295,7 @@ __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p,
     float mi = m[i], vi = v[i];
     const float gi = g[i];
     ss = fmaf(gi, gi, ss);
+    if (stop) continue;
     const float pi = adam_elem(mi, vi, p[i], gi, b1, b2, step_size, rbc2, eps);
     m[i] = mi;
     v[i] = vi;
@@ -294,9 +317,11 @@ __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p,
     __syncthreads();
   }
   if (threadIdx.x == 0) norm_part[blockIdx.x] = red[0];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    state[0] = step;
-    state[1] = step;
+  if constexpr (!GATE) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      state[0] = step;
+      state[1] = step;
+    }
   }
 }
 
@@ -309,17 +334,19 @@ __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p,
 // narrow-layer weight gradients; item_reduce) and update their parameters; the rest grid-stride
 // over the slab elements of [i_lo, n) — the range may be one head's slice of the flat vectors
 // (runtime/engine_hip.py).  Every block leaves its sum of squares in norm_part.
-template <int DT>
+template <int DT, bool GATE = false>
 __global__ __launch_bounds__(256) void gather_adam_kernel(
     const float* __restrict__ slab, const int* __restrict__ src_off, const int* __restrict__ src_meta,
     const float* __restrict__ part, int npblk, int npart, const int* __restrict__ red_col,
     const int* __restrict__ red_dst, int nitems, SlabRuns runs, float scale, float* __restrict__ loss_out,
     float* __restrict__ g, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int n, float lr,
-    float b1, float b2, float eps, float step, float* __restrict__ state, float* __restrict__ norm_part,
+    float b1, float b2, float eps, float step_host, float* __restrict__ state, float* __restrict__ norm_part,
     typename Prec<DT>::T* __restrict__ wimg, const int* __restrict__ w_map, const int* __restrict__ wt_map,
-    const float* __restrict__ qmul, F8Shadow f8) {
+    const float* __restrict__ qmul, F8Shadow f8, KlGate<GATE> kg) {
   using P = Prec<DT>;
   __shared__ float red[256];
+  const float step = GATE ? state[0] + 1.f : step_host;
+  const bool stop = kl_stopped(kg);
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
   const float step_size = lr / bc1;
@@ -329,12 +356,18 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
   // the optimizer-state loads are issued before the gradient is formed (they do not depend on
   // it), so their latency overlaps the slab loads'
   auto update = [&](int i, float gi, float mi, float vi, float pv, int wi, int wti) {
+    if (stop) {   // (gated and stopped: the gradient alone)
+      g[i] = gi;
+      return;
+    }
     adam_apply<DT>(i, gi, mi, vi, pv, wi, wti, g, p, m, v, b1, b2, step_size, rbc2, eps, wimg, qmul, f8);
   };
   if ((int)blockIdx.x < nrb) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      state[0] = step;
-      state[1] = step;
+    if constexpr (!GATE) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        state[0] = step;
+        state[1] = step;
+      }
     }
     float tot = 0.f;
     int j;
@@ -394,6 +427,28 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
     __syncthreads();
   }
   if (threadIdx.x == 0) norm_part[blockIdx.x] = red[0];
+}
+
+// target_kl: the gate, one launch after every step (ops/oracle.py kl_gate).  It is the only writer
+// of gate and, in gated mode, of the step counter: if the step just enqueued was applied (stop was
+// 0) the counter advances; then kl = fl32(sums[3] / max(sums[5], 1)) of that step's loss sums is
+// held against the target.  !(kl <= target), so a NaN trips too; a set stop stays set.
+__global__ __launch_bounds__(64) void kl_gate_kernel(const float* __restrict__ sums, float* __restrict__ gate,
+                                                     float* __restrict__ state, float target) {
+  if (threadIdx.x != 0) return;
+  const bool open = gate[0] == 0.f;
+  if (open) {
+    const float step = state[0] + 1.f;
+    state[0] = step;
+    state[1] = step;
+    gate[1] += 1.f;
+  }
+  const float kl = __fdiv_rn(sums[3], fmaxf(sums[5], 1.f));
+  gate[3] = kl;
+  if (open && !(kl <= target)) {
+    gate[0] = 1.f;
+    gate[2] = kl;
+  }
 }
 
 template <int DT>
@@ -621,41 +676,92 @@ extern "C" void launch_gae(const float* rewards, const float* values, const floa
 static int g_adam_fused = 1;   // A/B switch (set_adam_fused): 0 forces the sumsq + adam pair
 extern "C" void set_adam_fused(int on) { g_adam_fused = on; }
 
+namespace {
+template <bool GATE>
+void adam_dispatch(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2, float eps,
+                   float max_norm, float* state, float* norm_part, int nblk, void* wimg, const int* w_map,
+                   const int* wt_map, int dt, const float* img_scale, int host_step, const F8Shadow& f8,
+                   KlGate<GATE> kg, hipStream_t s) {
+  // (GATE: the step number is read on the device, so the one-launch form needs no host step)
+  if (max_norm <= 0.f && g_adam_fused && (GATE || host_step > 0)) {
+    const float step = (float)host_step;
+#define AN_ARGS p, g, m, v, n, lr, b1, b2, eps, step, state, norm_part
+    if (dt == DT_F32)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
+                         (float*)wimg, w_map, wt_map, img_scale, f8, kg);
+    else if (dt == DT_BF16)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
+                         (__bf16*)wimg, w_map, wt_map, img_scale, f8, kg);
+    else if (dt == DT_S3)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
+                         (S3Slot*)wimg, w_map, wt_map, img_scale, f8, kg);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
+                         (uint8_t*)wimg, w_map, wt_map, img_scale, f8, kg);
+#undef AN_ARGS
+    HIP_CHECK_LAUNCH();
+    return;
+  }
+  hipLaunchKernelGGL(sumsq_kernel<GATE>, dim3(nblk), dim3(256), 0, s, g, n, norm_part, state);
+#define AC_ARGS p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk
+  if (dt == DT_F32)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (float*)wimg,
+                       w_map, wt_map, img_scale, f8, kg);
+  else if (dt == DT_BF16)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (__bf16*)wimg,
+                       w_map, wt_map, img_scale, f8, kg);
+  else if (dt == DT_S3)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (S3Slot*)wimg,
+                       w_map, wt_map, img_scale, f8, kg);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (uint8_t*)wimg,
+                       w_map, wt_map, img_scale, f8, kg);
+#undef AC_ARGS
+  HIP_CHECK_LAUNCH();
+}
+
+template <bool GATE>
+void gather_adam_dispatch(const float* slab, const int* src_off, const int* src_meta, const float* part, int npblk,
+                          int npart, const int* red_col, const int* red_dst, int nitems, const SlabRuns& runs,
+                          float scale, float* loss_out, float* g, float* p, float* m, float* v, int n, float lr,
+                          float b1, float b2, float eps, int step, float* state, float* norm_part, int nblk,
+                          void* wimg, const int* w_map, const int* wt_map, int dt, const float* img_scale,
+                          const F8Shadow& f8, KlGate<GATE> kg, hipStream_t s) {
+#define GA_ARGS slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale, loss_out, g, p, m, \
+                v, n, lr, b1, b2, eps, \
+                (float)step, state, norm_part
+  if (dt == DT_F32)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
+                       (float*)wimg, w_map, wt_map, img_scale, f8, kg);
+  else if (dt == DT_BF16)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
+                       (__bf16*)wimg, w_map, wt_map, img_scale, f8, kg);
+  else if (dt == DT_S3)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
+                       (S3Slot*)wimg, w_map, wt_map, img_scale, f8, kg);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
+                       (uint8_t*)wimg, w_map, wt_map, img_scale, f8, kg);
+#undef GA_ARGS
+  HIP_CHECK_LAUNCH();
+}
+}  // namespace
+
 extern "C" void launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
                             float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
                             const int* w_map, const int* wt_map, int dt, const float* img_scale, int host_step,
                             const F8Shadow& f8, hipStream_t s) {
-  if (max_norm <= 0.f && g_adam_fused && host_step > 0) {
-    const float step = (float)host_step;
-    if (dt == DT_F32)
-      hipLaunchKernelGGL(adam_noclip_kernel<DT_F32>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
-                         step, state, norm_part, (float*)wimg, w_map, wt_map, img_scale, f8);
-    else if (dt == DT_BF16)
-      hipLaunchKernelGGL(adam_noclip_kernel<DT_BF16>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
-                         step, state, norm_part, (__bf16*)wimg, w_map, wt_map, img_scale, f8);
-    else if (dt == DT_S3)
-      hipLaunchKernelGGL(adam_noclip_kernel<DT_S3>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
-                         step, state, norm_part, (S3Slot*)wimg, w_map, wt_map, img_scale, f8);
-    else
-      hipLaunchKernelGGL(adam_noclip_kernel<DT_FP8>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps,
-                         step, state, norm_part, (uint8_t*)wimg, w_map, wt_map, img_scale, f8);
-    HIP_CHECK_LAUNCH();
-    return;
-  }
-  hipLaunchKernelGGL(sumsq_kernel, dim3(nblk), dim3(256), 0, s, g, n, norm_part, state);
-  if (dt == DT_F32)
-    hipLaunchKernelGGL(adam_kernel<DT_F32>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, max_norm,
-                       state, norm_part, nblk, (float*)wimg, w_map, wt_map, img_scale, f8);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL(adam_kernel<DT_BF16>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, max_norm,
-                       state, norm_part, nblk, (__bf16*)wimg, w_map, wt_map, img_scale, f8);
-  else if (dt == DT_S3)
-    hipLaunchKernelGGL(adam_kernel<DT_S3>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, max_norm,
-                       state, norm_part, nblk, (S3Slot*)wimg, w_map, wt_map, img_scale, f8);
-  else
-    hipLaunchKernelGGL(adam_kernel<DT_FP8>, dim3(nblk), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, max_norm,
-                       state, norm_part, nblk, (uint8_t*)wimg, w_map, wt_map, img_scale, f8);
-  HIP_CHECK_LAUNCH();
+  adam_dispatch<false>(p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk, wimg, w_map, wt_map, dt,
+                       img_scale, host_step, f8, KlGate<false>{}, s);
+}
+
+// target_kl: the gated forms (gate f32[4], read only; the step number is state[0] + 1) and the gate
+extern "C" void launch_adam_gated(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
+                                  float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
+                                  const int* w_map, const int* wt_map, int dt, const float* img_scale,
+                                  const F8Shadow& f8, const float* gate, hipStream_t s) {
+  adam_dispatch<true>(p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk, wimg, w_map, wt_map, dt,
+                      img_scale, 0, f8, KlGate<true>{gate}, s);
 }
 
 extern "C" void launch_gather_adam(const float* slab, const int* src_off, const int* src_meta, const float* part,
@@ -665,22 +771,26 @@ extern "C" void launch_gather_adam(const float* slab, const int* src_off, const 
                                    float* state, float* norm_part, int nblk, void* wimg, const int* w_map,
                                    const int* wt_map, int dt, const float* img_scale, const F8Shadow& f8,
                                    hipStream_t s) {
-#define GA_ARGS slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale, loss_out, g, p, m, \
-                v, n, lr, b1, b2, eps, \
-                (float)step, state, norm_part
-  if (dt == DT_F32)
-    hipLaunchKernelGGL(gather_adam_kernel<DT_F32>, dim3(nblk), dim3(256), 0, s, GA_ARGS, (float*)wimg, w_map, wt_map,
-                       img_scale, f8);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL(gather_adam_kernel<DT_BF16>, dim3(nblk), dim3(256), 0, s, GA_ARGS, (__bf16*)wimg, w_map,
-                       wt_map, img_scale, f8);
-  else if (dt == DT_S3)
-    hipLaunchKernelGGL(gather_adam_kernel<DT_S3>, dim3(nblk), dim3(256), 0, s, GA_ARGS, (S3Slot*)wimg, w_map,
-                       wt_map, img_scale, f8);
-  else
-    hipLaunchKernelGGL(gather_adam_kernel<DT_FP8>, dim3(nblk), dim3(256), 0, s, GA_ARGS, (uint8_t*)wimg, w_map,
-                       wt_map, img_scale, f8);
-#undef GA_ARGS
+  gather_adam_dispatch<false>(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale,
+                              loss_out, g, p, m, v, n, lr, b1, b2, eps, step, state, norm_part, nblk, wimg, w_map,
+                              wt_map, dt, img_scale, f8, KlGate<false>{}, s);
+}
+
+extern "C" void launch_gather_adam_gated(const float* slab, const int* src_off, const int* src_meta,
+                                         const float* part, int npblk, int npart, const int* red_col,
+                                         const int* red_dst, int nitems, const SlabRuns& runs, float scale,
+                                         float* loss_out, float* g, float* p, float* m, float* v, int n, float lr,
+                                         float b1, float b2, float eps, float* state, float* norm_part, int nblk,
+                                         void* wimg, const int* w_map, const int* wt_map, int dt,
+                                         const float* img_scale, const F8Shadow& f8, const float* gate,
+                                         hipStream_t s) {
+  gather_adam_dispatch<true>(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale,
+                             loss_out, g, p, m, v, n, lr, b1, b2, eps, 0, state, norm_part, nblk, wimg, w_map,
+                             wt_map, dt, img_scale, f8, KlGate<true>{gate}, s);
+}
+
+extern "C" void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s) {
+  hipLaunchKernelGGL(kl_gate_kernel, dim3(1), dim3(64), 0, s, loss_sums, gate, state, target_kl);
   HIP_CHECK_LAUNCH();
 }
 

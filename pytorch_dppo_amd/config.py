@@ -80,6 +80,12 @@ class Params:
                                          # rewards, episode returns and evaluation keep raw units.  Use with
                                          # reward_clip 0.  Refused with compat and with stats_stream on|auto.
     reward_norm_clip: float = 10.0       # r' clamped to +-this; <=0 disables
+    target_kl: float = 0.0               # > 0: after each step of an iteration, kl = approx_kl of that step's
+                                         # minibatch (summed over ranks); the first step with not (kl <= target_kl) is
+                                         # still applied, the iteration's later steps are not (ops/oracle.kl_gate; the
+                                         # decision is taken on the device).  Stopped steps still run their gradient
+                                         # kernels: no time is saved.  0: off.  Refused with loss=dppo_ref, compat,
+                                         # overlap_rollout and overlap_value_epochs.
     minibatches_per_epoch: int = 0       # 0 = buffer // batch_size (full pass); reference ppo.py uses 1
     total_env_steps: int = 0             # 0 = unbounded (use max_iters)
     max_iters: int = 0                   # 0 = unbounded
@@ -205,6 +211,22 @@ class Params:
             if self.stats_stream != "off":
                 raise ValueError("reward_norm is not built for stats_stream=on|auto: the return scale is merged on "
                                  "the compute stream before GAE reads it; use stats_stream=off")
+
+        self.target_kl = float(self.target_kl)
+        if not self.target_kl >= 0:
+            raise ValueError(f"target_kl must be >= 0 (0 = off): a KL estimate is never below a negative "
+                             f"target, got {self.target_kl}")
+        if self.target_kl > 0:
+            if self.loss == "dppo_ref":
+                raise ValueError("target_kl cannot be combined with loss=dppo_ref: that loss reports approx_kl = 0 by "
+                                 "construction, so the gate would never trip")
+            if self.compat:
+                raise ValueError("target_kl cannot be combined with compat: compat reproduces the reference, which "
+                                 "applies every update step")
+            if self.overlap_rollout or self.overlap_value_epochs:
+                raise ValueError("target_kl cannot be combined with overlap_rollout / overlap_value_epochs: they move "
+                                 "a value step to a side stream or behind the next rollout, and a gated step reads and "
+                                 "advances one device counter in stream order")
 
     def heartbeat_interval(self, world_size: int) -> float:
         """the heartbeat period in effect: heartbeat_s, or 5 s (auto) whenever there are peers"""

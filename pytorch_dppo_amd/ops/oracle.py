@@ -211,6 +211,32 @@ def clip_grad_norm_(g: torch.Tensor, max_norm: float) -> torch.Tensor:
     return norm
 
 
+def kl_gate(kl_sum, count, target_kl: float, gate) -> Tuple[list, bool]:
+    """``target_kl``'s gate after one step of an iteration (the twin of ``csrc/optim.hip`` kl_gate_kernel).
+
+    ``gate`` = ``[stop, applied, trip_kl, last_kl]`` (all 0 at the start of an iteration); ``kl_sum`` /
+    ``count`` are slots 3 and 5 of the step's 8 loss sums, summed over the ranks.  The step was applied
+    iff ``stop`` was 0 before this call (the caller applies it, or not, by that rule); then::
+
+        kl = fl32(kl_sum / max(count, 1))
+        if stop == 0 and not (kl <= target_kl):  stop = 1, trip_kl = kl      # a NaN KL also trips
+
+    so the step whose KL trips the gate is still applied and every later step of the iteration is not
+    (CleanRL's rule: the threshold is ``target_kl`` itself); a set ``stop`` stays set.
+    Returns ``(new gate as 4 python floats, applied)``; the fp32 roundings are the kernel's."""
+    f32 = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(())   # noqa: E731
+    stop, applied_n, trip, _ = (float(f32(x)) for x in gate)
+    applied = stop == 0.0
+    if applied:
+        applied_n = float(f32(applied_n) + 1.0)
+    n = f32(count)
+    n = n if bool(n > 1.0) else f32(1.0)            # fmaxf(count, 1): a NaN count gives 1
+    kl = float(f32(kl_sum) / n)
+    if applied and not (kl <= float(f32(target_kl))):
+        stop, trip = 1.0, kl
+    return [stop, applied_n, trip, kl], applied
+
+
 def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,
                lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
     """torch.optim.Adam (default, non-amsgrad, no weight decay) on flat buffers."""

@@ -293,7 +293,17 @@ class HipEngine:
         self.items = self._reduce_items(model)
         # ---- optimizer state ----
         n = model.num_params
-        self.grad_flat = torch.zeros(n, **f32)
+        # target_kl (docs/ARCHITECTURE.md §22): gate = [stop, applied, trip_kl, last_kl], written by the
+        # kl_gate launch that ends every step; the 8 loss sums sit behind the gradient in one allocation
+        # so that a gated step's one collective sums both over the ranks.  Only with the flag on.
+        self.gate: Optional[torch.Tensor] = None
+        self._grad_sums: Optional[torch.Tensor] = None
+        if float(getattr(params, "target_kl", 0.0)) > 0:
+            self.gate = torch.zeros(4, **f32)
+            self._grad_sums = torch.zeros(n + NPART_FIXED, **f32)
+            self.grad_flat = self._grad_sums[:n]
+        else:
+            self.grad_flat = torch.zeros(n, **f32)
         self.adam_m = torch.zeros(n, **f32)
         self.adam_v = torch.zeros(n, **f32)
         self.adam_state = torch.zeros(4, **f32)
@@ -332,7 +342,7 @@ class HipEngine:
         self._first_step = True
         self._loss_dev: Optional[torch.Tensor] = None
         self.local_stats: Optional[RunningObsStats] = None
-        self.loss_sums = torch.zeros(NPART_FIXED, **f32)
+        self.loss_sums = torch.zeros(NPART_FIXED, **f32) if self.gate is None else self._grad_sums[n:]
         self.metrics_buf = torch.zeros(2 + NPART_FIXED + 1, dtype=torch.float64, **dev)
         self.empty_x = torch.empty(0, dtype=self.sdtype, **dev)
         self.x_raw: Optional[torch.Tensor] = None   # compat Q8: raw bootstrap rows (values())
@@ -393,6 +403,12 @@ class HipEngine:
             self.ret_s12 = torch.zeros(2, dtype=torch.float64, **dev)
             self.ret_part = torch.zeros(2 * int(self.ext.ret_scan_nblk(T, E, 0)), dtype=torch.float64, **dev)
             self.metrics_buf = torch.zeros(2 + NPART_FIXED + 2, dtype=torch.float64, **dev)
+        # the metrics vector's slots behind metrics_pack's 11: return_std (reward_norm), then
+        # [stop, applied, trip_kl, applied since the start of training] (target_kl)
+        self._m_ret = 2 + NPART_FIXED + 1
+        self._m_gate = self._m_ret + (1 if self.ret_stats is not None else 0)
+        if self.gate is not None:
+            self.metrics_buf = torch.zeros(self._m_gate + 4, dtype=torch.float64, **dev)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -637,10 +653,28 @@ class HipEngine:
         self.train_rows = int(self.ext.train_rows(self.dt, self.layout, self.A, xb))
         self.ntrain_blk = self.ldT // self.train_rows
 
+    @property
+    def adam_step(self) -> int:
+        """Adam steps applied since the start of training.  Host-known without target_kl.  With it the
+        device decides which steps are applied and kl_gate alone advances the counter, so the number is
+        read from adam_state[0] (a host sync: checkpoints, params_changed — sync points already) and a
+        host write (a resume) goes to the device counter too."""
+        if self.gate is not None:
+            return int(self.adam_state[0].item())
+        return self._adam_step
+
+    @adam_step.setter
+    def adam_step(self, step: int) -> None:
+        self._adam_step = int(step)
+        if self.gate is not None:
+            self.adam_state[0] = float(step)
+            self.adam_state[1] = float(step)
+
     def params_changed(self) -> None:
         """re-pack the weight images from the fp32 master (after init / load / broadcast)."""
         self.ext.pack(self.model.flat.data, self.wimg, self.w_map, self.wt_map, self.dt, self.no_q)
-        self.adam_state[0] = float(self.adam_step)
+        if self.gate is None:     # (target_kl: adam_state[0] IS the step number, nothing to mirror)
+            self.adam_state[0] = float(self.adam_step)
         self.refresh_fwd_image()
 
     @torch.no_grad()
@@ -1260,6 +1294,8 @@ class HipEngine:
         if self.p.loss == "dppo_ref":   # only the reference loss reads the previous log_std
             self.log_std_old.copy_(self.model.flat.data[:self.A])
         self._first_step = True
+        if self.gate is not None:
+            self.gate.zero_()
 
     # ------------------------------------------------------------------------------------------
     def _minibatch(self, idx: Optional[torch.Tensor]):
@@ -1334,6 +1370,9 @@ class HipEngine:
         update take the whole-vector path."""
         p = self.p
         clip = p.max_grad_norm is not None and p.max_grad_norm > 0
+        if self.gate is not None:
+            self._gated_step(idx, extra_grad, allreduce, mean)
+            return
         if allreduce is None and self.can_fuse_apply(extra_grad):
             self.grad(idx, apply=True)          # world size 1: gather + Adam in one launch
             return
@@ -1381,6 +1420,29 @@ class HipEngine:
         self._head_adam(0, step_no)
         self.adam_step += 1
         self._norm_n = self.norm_regions[1][1]
+
+    def _gated_step(self, idx: Optional[torch.Tensor], extra_grad: float, allreduce, mean: bool) -> None:
+        """step() under target_kl (docs/ARCHITECTURE.md §22): the gradient kernels always run; the Adam
+        launch is the gated form (applied while gate[0] == 0, step number adam_state[0] + 1 read on the
+        device); the kl_gate launch ends the step.  World size 1 with can_fuse_apply: the joint gather +
+        Adam launch, gated.  Everything else: ONE gather of the whole gradient, ONE all-reduce of
+        [gradient | loss sums] (so every rank gates on the same bits; under grad_reduce=mean both KL
+        slots scale alike), ONE whole-vector Adam launch — the per-head Adam pairs and the side-stream
+        split are never gated."""
+        if allreduce is None and self.can_fuse_apply(extra_grad):
+            self.grad(idx, apply=True)
+        else:
+            if self.heads:
+                self._joint_grad(*self._minibatch(idx))
+            else:
+                self.grad(idx)
+            if allreduce is not None:
+                if getattr(allreduce, "in_stream", False):
+                    allreduce(self._grad_sums)          # sum / mean in stream order
+                else:
+                    self._reduce_wait(allreduce(self._grad_sums), self._grad_sums, mean)
+            self.apply(extra_grad)
+        self.ext.kl_gate(self.loss_sums, self.gate, self.adam_state, float(self.p.target_kl))
 
     def _split_step_side(self, allreduce) -> None:
         """the joint gradient is gathered: the value range's all-reduce (the side communicator) +
@@ -1499,6 +1561,15 @@ class HipEngine:
         b1, b2 = p.adam_betas
         src_off, src_meta = self.joint_src
         rc, rd = self.items["joint"]
+        if self.gate is not None:       # target_kl: the gated form (step number and stop flag on the device)
+            self.ext.gather_adam_gated(b["slab"], src_off, src_meta, self.part_joint, self.nhead_blk,
+                                       self.part_joint.shape[1], rc, rd, b["runs"], 1.0 / M, self.loss_sums,
+                                       self.grad_flat, self.model.flat.data, self.adam_m, self.adam_v, float(p.lr),
+                                       float(b1), float(b2), float(p.adam_eps), self.adam_state,
+                                       self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map, self.dt,
+                                       self.no_q, *self._f8(), self.gate)
+            self._norm_n = self.norm_n_whole
+            return
         self.ext.gather_adam(b["slab"], src_off, src_meta, self.part_joint, self.nhead_blk, self.part_joint.shape[1],
                              rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat, self.model.flat.data,
                              self.adam_m, self.adam_v, float(p.lr), float(b1), float(b2), float(p.adam_eps),
@@ -1548,7 +1619,8 @@ class HipEngine:
         if apply:
             assert self.can_fuse_apply(), "fused gather + Adam is not available here"
             self._launch_grad(idx_t, first, xt_ready, fused_apply=True)
-            self.adam_step += 1
+            if self.gate is None:       # (target_kl: kl_gate advances the device counter)
+                self.adam_step += 1
             self._norm_n = self.norm_n_whole
         else:
             self._launch_grad(idx_t, first, xt_ready)
@@ -1570,6 +1642,14 @@ class HipEngine:
                 self.log_std_old.copy_(self.model.flat.data[:self.A])
             b1, b2 = p.adam_betas
             rc, rd = self.items["legacy"]
+            if self.gate is not None:   # target_kl: the gated form
+                self.ext.gather_adam_gated(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk,
+                                           self.npart, rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat,
+                                           self.model.flat.data, self.adam_m, self.adam_v, float(p.lr), float(b1),
+                                           float(b2), float(p.adam_eps), self.adam_state,
+                                           self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map,
+                                           self.dt, self.no_q, *self._f8(), self.gate)
+                return
             self.ext.gather_adam(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk,
                                  self.npart, rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat,
                                  self.model.flat.data, self.adam_m, self.adam_v, float(p.lr), float(b1),
@@ -1592,6 +1672,14 @@ class HipEngine:
             self.grad_flat.add_(extra_grad)
         mx = float(p.max_grad_norm) if (p.max_grad_norm is not None and p.max_grad_norm > 0) else 0.0
         b1, b2 = p.adam_betas
+        if self.gate is not None:
+            # target_kl: the gated form — one launch without clipping, the sumsq + adam pair with it;
+            # the step number and the stop flag are read on the device, kl_gate advances the counter
+            self.ext.adam_gated(self.model.flat.data, self.grad_flat, self.adam_m, self.adam_v, float(p.lr), float(b1),
+                                float(b2), float(p.adam_eps), mx, self.adam_state, self.norm_part[:self.norm_n_whole],
+                                self.wimg, self.w_map, self.wt_map, self.dt, self.no_q, *self._f8(), self.gate)
+            self._norm_n = self.norm_n_whole
+            return None
         # the host knows the step number: one fused kernel without clipping
         self.ext.adam(self.model.flat.data, self.grad_flat, self.adam_m, self.adam_v, float(p.lr), float(b1),
                       float(b2), float(p.adam_eps), mx, self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg,
@@ -1620,10 +1708,14 @@ class HipEngine:
             side.wait_stream(torch.cuda.current_stream(self.device))
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             self.ext.metrics_pack(ep2, self._loss_dev, self.norm_part[:n], self.metrics_buf)
-            if self.ret_stats is not None:      # return_std = sqrt(M2 / n) rides in the last slot
-                tail = self.metrics_buf[-1:]
+            if self.ret_stats is not None:      # return_std = sqrt(M2 / n) rides behind the 11
+                tail = self.metrics_buf[self._m_ret:self._m_ret + 1]
                 torch.mul(self.ret_stats.mean_diff, 1.0 / max(self.ret_stats.n, 1.0), out=tail)
                 tail.sqrt_()
+            if self.gate is not None:           # [stop, applied, trip_kl | steps applied since the start]
+                g0 = self._m_gate
+                self.metrics_buf[g0:g0 + 3].copy_(self.gate[:3])
+                self.metrics_buf[g0 + 3:g0 + 4].copy_(self.adam_state[0:1])
         return self.metrics_buf
 
     def loss_vector(self) -> Optional[torch.Tensor]:

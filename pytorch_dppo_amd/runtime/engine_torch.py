@@ -71,6 +71,10 @@ class TorchEngine:
         self.adam_m = torch.zeros(n, **f32)
         self.adam_v = torch.zeros(n, **f32)
         self.adam_step = 0
+        # target_kl: [stop, applied, trip_kl, last_kl] of the current iteration (ops/oracle.kl_gate) and
+        # the last step's (KL sum, row count); only with the flag on
+        self.gate: Optional[list] = [0.0, 0.0, 0.0, 0.0] if params.target_kl > 0 else None
+        self.kl_pair: Optional[torch.Tensor] = None
         self.flat_old = model.flat.detach().clone()  # dppo_ref "model_old" (train.py:128-129,164)
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.obs = env.reset().to(device)
@@ -199,6 +203,8 @@ class TorchEngine:
 
     def begin_update(self) -> None:
         self.flat_old.copy_(self.model.flat.detach())
+        if self.gate is not None:
+            self.gate = [0.0, 0.0, 0.0, 0.0]
 
     # -- update ----------------------------------------------------------------------------
     def grad(self, idx: torch.Tensor) -> Dict[str, float]:
@@ -229,7 +235,19 @@ class TorchEngine:
         out["loss"].backward()
         self.grad_flat.copy_(self.model.flat.grad)
         self._last = {k: float(v.detach()) for k, v in out.items()}
+        if self.gate is not None:
+            # target_kl: slots 3 and 5 of the HIP engine's loss sums (the estimator's sum, the row count)
+            M = float(idx.numel())
+            self.kl_pair = torch.stack([out["approx_kl"].detach().to(torch.float32) * M,
+                                        torch.tensor(M, dtype=torch.float32, device=self.device)])
         return self._last
+
+    @torch.no_grad()
+    def skip(self) -> float:
+        """target_kl, a stopped step: nothing moves; the reported gradient norm is this step's, as the
+        HIP engine's stopped launches leave it"""
+        self._norm = float(torch.linalg.vector_norm(self.grad_flat))
+        return self._norm
 
     @torch.no_grad()
     def apply(self, extra_grad: float = 0.0) -> float:

@@ -29,6 +29,7 @@ import torch
 from ..config import Params
 from ..envs import get_spec, host_spec, import_env_module, make_vec_env
 from ..models.actor_critic import ActorCritic
+from ..ops import oracle
 from ..parallel.dist import DistContext
 from ..utils import rng
 from ..utils.metrics import MetricsLogger, PhaseTimer
@@ -186,6 +187,7 @@ class DPPOWorker:
         eng.begin_update()
         N, mb, nmb = self._minibatch_plan()
         mean = p.grad_reduce == "mean"
+        gated = p.target_kl > 0
         self._perm_gen.manual_seed((p.seed * 1000003 + self.ctx.rank * 7919 + self.iteration) & 0x7FFFFFFF)
         for epoch in range(p.num_epoch):
             if mb >= N and nmb == 1:
@@ -216,10 +218,23 @@ class DPPOWorker:
                     # async all-reduce overlapping the other head's kernels (HipEngine.step)
                     ar = self.ctx.grad_allreduce_fn(mean)
                     eng.step(idx, extra, allreduce=ar, mean=mean, last=last)
-                    self.updates += 1
+                    if not gated:     # (target_kl: the device counts the applied steps)
+                        self.updates += 1
                     continue
                 deferred = p.overlap_rollout and last and not mean and self.ctx.collective
                 eng.grad(idx)
+                if gated:
+                    # target_kl (ops/oracle.kl_gate): the gradient and the KL pair are summed over the
+                    # ranks; the step is applied while the gate is open, then the gate sees its KL
+                    self.ctx.allreduce_grads(eng.grad_flat, mean=mean)
+                    pair = self.ctx.allreduce_tensor_(eng.kl_pair)
+                    if eng.gate[0] == 0.0:
+                        eng.apply(extra)
+                        self.updates += 1
+                    else:
+                        eng.skip()
+                    eng.gate, _ = oracle.kl_gate(pair[0], pair[1], p.target_kl, eng.gate)
+                    continue
                 if deferred:
                     work = self.ctx.allreduce_grads(eng.grad_flat, async_op=True)
                     self._pending = (work, extra)      # applied after the next rollout launch
@@ -272,8 +287,14 @@ class DPPOWorker:
             loss_dev = flat
         else:
             flat, loss_dev = self._stage_parts(ro)
-            if self.p.reward_norm:     # return_std rides in the last slot (pack_metrics wrote its own)
+            if self.p.reward_norm:     # return_std rides behind the vector (pack_metrics wrote its own)
                 flat = torch.cat([flat, eng.ret_stats.std().to(flat.device)])
+            if self.p.target_kl > 0:   # [stop, applied, trip_kl | steps applied since the start], likewise
+                if torch.is_tensor(eng.gate):      # (the GPU engine without a device rollout's ep2)
+                    tail = torch.cat([eng.gate[:3], eng.adam_state[0:1]])
+                else:
+                    tail = torch.tensor(list(eng.gate[:3]) + [float(self.updates)], dtype=torch.float64)
+                flat = torch.cat([flat, tail.to(flat.device, torch.float64)])
         if dev.type == "cuda":
             # the stream the metrics were packed on (the side stream while the overlapped value
             # step runs there)
@@ -308,6 +329,9 @@ class DPPOWorker:
         if hasattr(self.engine, "raise_if_failed"):
             self.engine.raise_if_failed()        # (a timed-out per-step filter launch: never report it)
         v = st["host"].tolist()
+        kl_gate = None
+        if p.target_kl > 0:
+            kl_gate, v = v[-4:], v[:-4]
         ret_std = v.pop() if p.reward_norm else None
         ep_ret, ep_cnt = v[0], v[1]
         if st["has_loss"]:
@@ -324,6 +348,12 @@ class DPPOWorker:
              "grad_norm": gnorm, **losses, **phases}
         if ret_std is not None:
             m["return_std"] = ret_std
+        if kl_gate is not None:
+            # target_kl: `updates` is the cumulative number of steps APPLIED (the device's counter)
+            stopped = kl_gate[0] != 0.0
+            m.update(kl_stopped=stopped, steps_applied=int(kl_gate[1]), kl_trip=kl_gate[2] if stopped else None,
+                     updates=int(kl_gate[3]))
+            self.updates = max(self.updates, int(kl_gate[3]))
         if p.verify_sync_every and st["iteration"] % p.verify_sync_every == 0:
             self.quiesce()                       # the checksum reads the value head too
             m["replicas_in_sync"] = self.ctx.verify_replicas(self.model.flat.data)
@@ -426,6 +456,8 @@ class DPPOWorker:
     def trainer_state(self) -> Dict:
         self.flush_pending()
         eng = self.engine
+        if self.p.target_kl > 0:
+            self.updates = int(eng.adam_step)    # the applied count (GPU engine: read from the device)
         return {"adam_m": eng.adam_m.detach().cpu(), "adam_v": eng.adam_v.detach().cpu(),
                 "adam_step": eng.adam_step, "obs_stats": self.stats.state_dict(),
                 "iteration": self.iteration, "env_steps": self.env_steps, "updates": self.updates,
