@@ -805,24 +805,44 @@ SlabRuns make_runs(const std::vector<int64_t>& v, int64_t n) {
   return r;
 }
 
-void grad_gather(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
-                 int64_t nblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, double scale,
-                 torch::Tensor grad, torch::Tensor loss_out, std::vector<int64_t> runs) {
-  const int64_t n = grad.numel();
-  const SlabRuns sr = make_runs(runs, n);
-  check(grad, "grad", at::kFloat, n);
+using CT = const torch::Tensor&;
+
+// GatherArgs (csrc/kernels.h) of a gather over a flat range of n elements, checked
+GatherArgs gather_args(CT slab, CT src_off, CT src_meta, CT part, int64_t npblk, int64_t npart, CT red_col, CT red_dst,
+                       const std::vector<int64_t>& runs, double scale, CT loss_out, int64_t n) {
   check(src_off, "src_off", at::kInt, n);
   check(src_meta, "src_meta", at::kInt, n);
   check(slab, "slab", at::kFloat, 1);
-  check(part, "part", at::kFloat, nblk * npart);
+  check(part, "part", at::kFloat, npblk * npart);
   check(loss_out, "loss_out", at::kFloat, 8);
   const int64_t nitems = red_col.numel();
   check(red_col, "red_col", at::kInt, nitems);
   check(red_dst, "red_dst", at::kInt, nitems);
   TORCH_CHECK(red_dst.numel() == nitems, "red_col / red_dst sizes");
-  launch_grad_gather(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
-                     part.data_ptr<float>(), (int)nblk, (int)npart, red_col.data_ptr<int>(), red_dst.data_ptr<int>(),
-                     (int)nitems, (float)scale, grad.data_ptr<float>(), sr, loss_out.data_ptr<float>(), cur_stream());
+  GatherArgs ga{};
+  ga.slab = slab.data_ptr<float>();
+  ga.src_off = src_off.data_ptr<int>();
+  ga.src_meta = src_meta.data_ptr<int>();
+  ga.part = part.data_ptr<float>();
+  ga.npblk = (int)npblk;
+  ga.npart = (int)npart;
+  ga.red_col = red_col.data_ptr<int>();
+  ga.red_dst = red_dst.data_ptr<int>();
+  ga.nitems = (int)nitems;
+  ga.runs = make_runs(runs, n);
+  ga.scale = (float)scale;
+  ga.loss_out = loss_out.data_ptr<float>();
+  return ga;
+}
+
+void grad_gather(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
+                 int64_t nblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, double scale,
+                 torch::Tensor grad, torch::Tensor loss_out, std::vector<int64_t> runs) {
+  const int64_t n = grad.numel();
+  check(grad, "grad", at::kFloat, n);
+  const GatherArgs ga =
+      gather_args(slab, src_off, src_meta, part, nblk, npart, red_col, red_dst, runs, scale, loss_out, n);
+  launch_grad_gather(ga, grad.data_ptr<float>(), cur_stream());
   after_launch(__func__);
 }
 
@@ -881,8 +901,12 @@ void obs_merge(torch::Tensor s12, double count, double n_a, torch::Tensor shift,
   after_launch(__func__);
 }
 
-void gae(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor adv, torch::Tensor ret,
-         double gamma, double lam, int64_t mode, int64_t seg) {
+// The GAE scan over [T,E] buffers (csrc/optim.hip launch_gae_rn).  boot [T,E] (bootstrap_time_limit: V of a
+// truncated step's final observation, 0 elsewhere): an empty tensor is the scan without it.  scale (reward_norm:
+// the reward enters as r' = clamp(fl32(r * scale[0]), +-rclip), rclip <= 0: no clamp): a device scalar read by the
+// kernel, null is the scan without it.
+void gae_impl(const char* fn, CT rewards, CT values, CT dones, CT boot, const torch::Tensor* scale, double rclip,
+              CT adv, CT ret, double gamma, double lam, int64_t mode, int64_t seg) {
   TORCH_CHECK(seg >= 0, "segment length must be >= 0 (0: no segment cut)");
   TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
   TORCH_CHECK(mode >= 0 && mode <= 2, "gae mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
@@ -890,49 +914,7 @@ void gae(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch
   check(rewards, "rewards", at::kFloat, T * E);
   check(values, "values", at::kFloat, (T + 1) * E);
   check(dones, "dones", at::kFloat, T * E);
-  check(adv, "adv", at::kFloat, T * E);
-  check(ret, "ret", at::kFloat, T * E);
-  launch_gae(rewards.data_ptr<float>(), values.data_ptr<float>(), dones.data_ptr<float>(), adv.data_ptr<float>(),
-             ret.data_ptr<float>(), (int)T, (int)E, (float)gamma, (float)lam, (int)mode, (int)seg, cur_stream());
-  after_launch(__func__);
-}
-
-// gae() with boot [T,E] (bootstrap_time_limit: V of a truncated step's final observation, 0 elsewhere;
-// an empty tensor: gae() itself)
-void gae_boot(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor adv,
-              torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
-  TORCH_CHECK(seg >= 0, "segment length must be >= 0 (0: no segment cut)");
-  TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "gae mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
-  const int64_t T = rewards.size(0), E = rewards.size(1);
-  check(rewards, "rewards", at::kFloat, T * E);
-  check(values, "values", at::kFloat, (T + 1) * E);
-  check(dones, "dones", at::kFloat, T * E);
-  check(adv, "adv", at::kFloat, T * E);
-  check(ret, "ret", at::kFloat, T * E);
-  const float* b = nullptr;
-  if (boot.defined() && boot.numel() > 0) {
-    check(boot, "boot", at::kFloat, T * E);
-    b = boot.data_ptr<float>();
-  }
-  launch_gae_boot(rewards.data_ptr<float>(), values.data_ptr<float>(), dones.data_ptr<float>(), b,
-                  adv.data_ptr<float>(), ret.data_ptr<float>(), (int)T, (int)E, (float)gamma, (float)lam, (int)mode,
-                  (int)seg, cur_stream());
-  after_launch(__func__);
-}
-
-// gae_boot() on the reward r' = clamp(fl32(r * scale[0]), +-rclip) (reward_norm; rclip <= 0: no clamp): scale
-// is a device scalar, read by the kernel
-void gae_rn(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor scale,
-            double rclip, torch::Tensor adv, torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
-  TORCH_CHECK(seg >= 0, "segment length must be >= 0 (0: no segment cut)");
-  TORCH_CHECK(rewards.dim() == 2, "rewards [T,E]");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "gae mode: 0 auto, 1 per-env lanes, 2 parallel-in-time scan");
-  const int64_t T = rewards.size(0), E = rewards.size(1);
-  check(rewards, "rewards", at::kFloat, T * E);
-  check(values, "values", at::kFloat, (T + 1) * E);
-  check(dones, "dones", at::kFloat, T * E);
-  check(scale, "scale", at::kFloat, 1);
+  if (scale != nullptr) check(*scale, "scale", at::kFloat, 1);
   check(adv, "adv", at::kFloat, T * E);
   check(ret, "ret", at::kFloat, T * E);
   const float* b = nullptr;
@@ -941,9 +923,24 @@ void gae_rn(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, to
     b = boot.data_ptr<float>();
   }
   launch_gae_rn(rewards.data_ptr<float>(), values.data_ptr<float>(), dones.data_ptr<float>(), b,
-                scale.data_ptr<float>(), (float)rclip, adv.data_ptr<float>(), ret.data_ptr<float>(), (int)T, (int)E,
-                (float)gamma, (float)lam, (int)mode, (int)seg, cur_stream());
-  after_launch(__func__);
+                scale != nullptr ? scale->data_ptr<float>() : nullptr, (float)rclip, adv.data_ptr<float>(),
+                ret.data_ptr<float>(), (int)T, (int)E, (float)gamma, (float)lam, (int)mode, (int)seg, cur_stream());
+  after_launch(fn);
+}
+
+void gae(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor adv, torch::Tensor ret,
+         double gamma, double lam, int64_t mode, int64_t seg) {
+  gae_impl(__func__, rewards, values, dones, torch::Tensor(), nullptr, 0.0, adv, ret, gamma, lam, mode, seg);
+}
+
+void gae_boot(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor adv,
+              torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
+  gae_impl(__func__, rewards, values, dones, boot, nullptr, 0.0, adv, ret, gamma, lam, mode, seg);
+}
+
+void gae_rn(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones, torch::Tensor boot, torch::Tensor scale,
+            double rclip, torch::Tensor adv, torch::Tensor ret, double gamma, double lam, int64_t mode, int64_t seg) {
+  gae_impl(__func__, rewards, values, dones, boot, &scale, rclip, adv, ret, gamma, lam, mode, seg);
 }
 
 // reward_norm: the discounted-return scan of a rollout (csrc/retnorm.hip).  ret_acc [E] is updated in place,
@@ -1015,14 +1012,13 @@ const float* gate_ptr(const torch::Tensor& gate) {
   return gate.data_ptr<float>();
 }
 
-// gate == nullptr: the ungated launch (host_step as below); else the gated form (the step number is
-// state[0] + 1 on the device, host_step unused)
-using CT = const torch::Tensor&;
-void adam_impl(const char* fn, CT p, CT g, CT m, CT v, double lr, double b1, double b2, double eps, double max_norm,
-               CT state, CT norm_part, CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul, int64_t host_step, CT f8_img,
-               CT f8_lid, CT f8_qs, const torch::Tensor* gate) {
-  // host_step >= 1: the step number of this update (eager launch: one fused kernel when there is
-  // no clipping); 0: read the device counter (graph replay)
+// AdamArgs (csrc/kernels.h) of one optimizer launch over the flat range p, checked.  host_step >= 1: the step
+// number of this update (eager launch: one fused kernel when there is no clipping); 0: read the device counter
+// (graph replay).  gate: an empty tensor is the ungated launch; else target_kl's gated step — applied only while
+// gate[0] == 0, the step number state[0] + 1 read on the device (host_step unused).
+AdamArgs adam_args(CT p, CT g, CT m, CT v, double lr, double b1, double b2, double eps, double max_norm,
+                   int64_t host_step, CT state, CT norm_part, CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul,
+                   CT f8_img, CT f8_lid, CT f8_qs, CT gate) {
   const int64_t n = p.numel();
   check(p, "p", at::kFloat, n);
   check(g, "g", at::kFloat, n);
@@ -1035,38 +1031,41 @@ void adam_impl(const char* fn, CT p, CT g, CT m, CT v, double lr, double b1, dou
   const int nblk = (int)norm_part.numel();
   check(norm_part, "norm_part", at::kFloat, nblk);
   TORCH_CHECK(nblk >= 1 && nblk <= 4096, "norm_part size");
-  const float* q = nullptr;
-  if (qmul.defined() && qmul.numel() > 0) { check(qmul, "qmul", at::kFloat, n); q = qmul.data_ptr<float>(); }
-  if (gate != nullptr)
-    launch_adam_gated(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n,
-                      (float)lr, (float)b1, (float)b2, (float)eps, (float)max_norm, state.data_ptr<float>(),
-                      norm_part.data_ptr<float>(), nblk, wimg.data_ptr(), w_map.data_ptr<int>(),
-                      wt_map.data_ptr<int>(), (int)dt, q, f8_shadow(f8_img, f8_lid, f8_qs, n), gate_ptr(*gate),
-                      cur_stream());
-  else
-    launch_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr,
-                (float)b1, (float)b2, (float)eps, (float)max_norm, state.data_ptr<float>(), norm_part.data_ptr<float>(),
-                nblk, wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q, (int)host_step,
-                f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
-  after_launch(fn);
+  AdamArgs a{};
+  a.p = p.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.m = m.data_ptr<float>();
+  a.v = v.data_ptr<float>();
+  a.n = (int)n;
+  a.lr = (float)lr;
+  a.b1 = (float)b1;
+  a.b2 = (float)b2;
+  a.eps = (float)eps;
+  a.max_norm = (float)max_norm;
+  a.state = state.data_ptr<float>();
+  a.norm_part = norm_part.data_ptr<float>();
+  a.nblk = nblk;
+  a.wimg = wimg.data_ptr();
+  a.w_map = w_map.data_ptr<int>();
+  a.wt_map = wt_map.data_ptr<int>();
+  a.dt = (int)dt;
+  if (qmul.defined() && qmul.numel() > 0) { check(qmul, "qmul", at::kFloat, n); a.img_scale = qmul.data_ptr<float>(); }
+  a.f8 = f8_shadow(f8_img, f8_lid, f8_qs, n);
+  if (gate.defined() && gate.numel() > 0) a.gate = gate_ptr(gate);
+  a.host_step = a.gate != nullptr ? 0 : (int)host_step;
+  return a;
 }
 
+// Adam (+ clip) over a flat range: one launch without clipping when the step number is known (host_step >= 1, or
+// gated), else the sumsq + adam pair
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
           double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
           torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, int64_t host_step,
-          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
-  adam_impl(__func__, p, g, m, v, lr, b1, b2, eps, max_norm, state, norm_part, wimg, w_map, wt_map, dt, qmul,
-            host_step, f8_img, f8_lid, f8_qs, nullptr);
-}
-
-// target_kl: adam() as a gated step — applied only while gate[0] == 0, step number state[0] + 1 read
-// on the device; one launch without clipping, the sumsq + adam pair with it
-void adam_gated(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
-                double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
-                torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, torch::Tensor f8_img,
-                torch::Tensor f8_lid, torch::Tensor f8_qs, torch::Tensor gate) {
-  adam_impl(__func__, p, g, m, v, lr, b1, b2, eps, max_norm, state, norm_part, wimg, w_map, wt_map, dt, qmul, 0,
-            f8_img, f8_lid, f8_qs, &gate);
+          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs, torch::Tensor gate) {
+  launch_adam(adam_args(p, g, m, v, lr, b1, b2, eps, max_norm, host_step, state, norm_part, wimg, w_map, wt_map, dt,
+                        qmul, f8_img, f8_lid, f8_qs, gate),
+              cur_stream());
+  after_launch(__func__);
 }
 
 // target_kl: the gate after a step (csrc/optim.hip kl_gate_kernel; ops/oracle.py kl_gate)
@@ -1079,82 +1078,25 @@ void kl_gate(torch::Tensor loss_sums, torch::Tensor gate, torch::Tensor state, d
   after_launch(__func__);
 }
 
-// grad_gather (reduce items + slab elements of [i_lo, n)) and the no-clip Adam step in one
-// launch (world size 1: nothing runs between them).  Bit-identical parameters to grad_gather ->
-// adam(host_step).  The flat tensors may be one head's slice (red_dst indexes the slice).
-void gather_adam_impl(const char* fn, CT slab, CT src_off, CT src_meta, CT part, int64_t npblk, int64_t npart,
-                      CT red_col, CT red_dst, const std::vector<int64_t>& runs, double scale, CT loss_out, CT g, CT p,
-                      CT m, CT v, double lr, double b1, double b2, double eps, int64_t step, CT state, CT norm_part,
-                      CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul, CT f8_img, CT f8_lid, CT f8_qs,
-                      const torch::Tensor* gate) {
-  const int64_t n = p.numel();
-  check(p, "p", at::kFloat, n);
-  check(g, "g", at::kFloat, n);
-  check(m, "m", at::kFloat, n);
-  check(v, "v", at::kFloat, n);
-  check(src_off, "src_off", at::kInt, n);
-  check(src_meta, "src_meta", at::kInt, n);
-  check(slab, "slab", at::kFloat, 1);
-  check(part, "part", at::kFloat, npblk * npart);
-  check(loss_out, "loss_out", at::kFloat, 8);
-  check(state, "state", at::kFloat, 4);
-  check(w_map, "w_map", at::kInt, n);
-  check(wt_map, "wt_map", at::kInt, n);
-  check(wimg, "wimg", storage_type((int)dt), 1);
-  const int64_t nitems = red_col.numel();
-  check(red_col, "red_col", at::kInt, nitems);
-  check(red_dst, "red_dst", at::kInt, nitems);
-  TORCH_CHECK(red_dst.numel() == nitems, "red_col / red_dst");
-  const SlabRuns sr = make_runs(runs, n);
-  TORCH_CHECK(gate != nullptr || step >= 1, "gather_adam needs the host step number (eager launches only)");
-  const int nblk = (int)norm_part.numel();
-  check(norm_part, "norm_part", at::kFloat, nblk);
-  TORCH_CHECK(nblk > item_blocks((int)nitems) && nblk <= 4096, "norm_part must hold more blocks than the reduce blocks");
-  const float* q = nullptr;
-  if (qmul.defined() && qmul.numel() > 0) { check(qmul, "qmul", at::kFloat, n); q = qmul.data_ptr<float>(); }
-  if (gate != nullptr)
-    launch_gather_adam_gated(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
-                             part.data_ptr<float>(), (int)npblk, (int)npart, red_col.data_ptr<int>(),
-                             red_dst.data_ptr<int>(), (int)nitems, sr, (float)scale, loss_out.data_ptr<float>(),
-                             g.data_ptr<float>(), p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n,
-                             (float)lr, (float)b1, (float)b2, (float)eps, state.data_ptr<float>(),
-                             norm_part.data_ptr<float>(), nblk, wimg.data_ptr(), w_map.data_ptr<int>(),
-                             wt_map.data_ptr<int>(), (int)dt, q, f8_shadow(f8_img, f8_lid, f8_qs, n), gate_ptr(*gate),
-                             cur_stream());
-  else
-    launch_gather_adam(slab.data_ptr<float>(), src_off.data_ptr<int>(), src_meta.data_ptr<int>(),
-                       part.data_ptr<float>(), (int)npblk, (int)npart, red_col.data_ptr<int>(), red_dst.data_ptr<int>(),
-                       (int)nitems, sr, (float)scale, loss_out.data_ptr<float>(), g.data_ptr<float>(),
-                       p.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), (int)n, (float)lr, (float)b1,
-                       (float)b2, (float)eps, (int)step, state.data_ptr<float>(), norm_part.data_ptr<float>(), nblk,
-                       wimg.data_ptr(), w_map.data_ptr<int>(), wt_map.data_ptr<int>(), (int)dt, q,
-                       f8_shadow(f8_img, f8_lid, f8_qs, n), cur_stream());
-  after_launch(fn);
-}
-
+// grad_gather (reduce items + slab elements of the runs) and the no-clip Adam step in one launch (world size 1:
+// nothing runs between them).  Bit-identical parameters to grad_gather -> adam(host_step).  The flat tensors may be
+// one head's slice (red_dst indexes the slice).  Gated (adam_args) it takes no host step number, and with gate[0]
+// set it still writes g, loss_out and norm_part; p, m, v and the images stay.
 void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
                  int64_t npblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, std::vector<int64_t> runs,
                  double scale, torch::Tensor loss_out, torch::Tensor g, torch::Tensor p, torch::Tensor m,
                  torch::Tensor v, double lr, double b1, double b2, double eps, int64_t step, torch::Tensor state,
                  torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map, torch::Tensor wt_map, int64_t dt,
-                 torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs) {
-  gather_adam_impl(__func__, slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, g,
-                   p, m, v, lr, b1, b2, eps, step, state, norm_part, wimg, w_map, wt_map, dt, qmul, f8_img, f8_lid,
-                   f8_qs, nullptr);
-}
-
-// target_kl: gather_adam() as a gated step (no host step number: state[0] + 1 on the device).  With
-// gate[0] set it still writes g, loss_out and norm_part; p, m, v and the images stay.
-void gather_adam_gated(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
-                       int64_t npblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst,
-                       std::vector<int64_t> runs, double scale, torch::Tensor loss_out, torch::Tensor g,
-                       torch::Tensor p, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2, double eps,
-                       torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map,
-                       torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid,
-                       torch::Tensor f8_qs, torch::Tensor gate) {
-  gather_adam_impl(__func__, slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, g,
-                   p, m, v, lr, b1, b2, eps, 0, state, norm_part, wimg, w_map, wt_map, dt, qmul, f8_img, f8_lid,
-                   f8_qs, &gate);
+                 torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs,
+                 torch::Tensor gate) {
+  const AdamArgs a = adam_args(p, g, m, v, lr, b1, b2, eps, 0.0, step, state, norm_part, wimg, w_map, wt_map, dt, qmul,
+                               f8_img, f8_lid, f8_qs, gate);
+  const GatherArgs ga =
+      gather_args(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, p.numel());
+  TORCH_CHECK(a.gate != nullptr || step >= 1, "gather_adam needs the host step number (eager launches only)");
+  TORCH_CHECK(a.nblk > item_blocks(ga.nitems), "norm_part must hold more blocks than the reduce blocks");
+  launch_gather_adam(ga, a, cur_stream());
+  after_launch(__func__);
 }
 
 void fp8_refresh(torch::Tensor p, torch::Tensor lid, torch::Tensor qscale, torch::Tensor part, torch::Tensor wimg,
@@ -1250,8 +1192,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("obs_moments_nblk", &obs_moments_nblk);
   m.def("adam", &adam);
   m.def("gather_adam", &gather_adam);
-  m.def("adam_gated", &adam_gated);
-  m.def("gather_adam_gated", &gather_adam_gated);
   m.def("kl_gate", &kl_gate);
   m.def("pack", &pack);
   m.def("debug_invalid_launch", &debug_invalid_launch);

@@ -14,6 +14,8 @@
 #include <hip/hip_fp8.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
@@ -117,6 +119,15 @@ template <> struct Prec<DT_S3> {
   }
 };
 template <int DT> struct IsSplit { static constexpr bool value = DT == DT_S3; };
+
+// f(integral_constant<int, DT>) for a run-time precision code
+template <typename F>
+auto dispatch_dt(int dt, F&& f) {
+  if (dt == DT_F32) return f(std::integral_constant<int, DT_F32>{});
+  if (dt == DT_BF16) return f(std::integral_constant<int, DT_BF16>{});
+  if (dt == DT_S3) return f(std::integral_constant<int, DT_S3>{});
+  return f(std::integral_constant<int, DT_FP8>{});
+}
 
 // OCP e4m3fn (gfx950 native; NOT the MI300 fnuz encoding)
 template <> struct Prec<DT_FP8> {

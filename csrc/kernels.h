@@ -267,6 +267,52 @@ struct SlabRuns {
 constexpr int ITEM_IPB = 32;
 inline __host__ __device__ int item_blocks(int nitems) { return (nitems + ITEM_IPB - 1) / ITEM_IPB; }
 
+// A gradient gather (csrc/wgrad.hip grad_gather_kernel, csrc/optim.hip gather_adam_kernel): the
+// slab elements of `runs` as split-K slab sums (src_off / src_meta, indexed by flat element) and
+// the reduce items as column sums of the npblk x npart per-workgroup partial rows.  The flat
+// vectors may be one head's slice (red_dst then indexes the slice).
+struct GatherArgs {
+  const float* slab;
+  const int* src_off;
+  const int* src_meta;
+  const float* part;
+  int npblk, npart;
+  const int* red_col;   // [nitems] partial-row column of each reduce item
+  const int* red_dst;   // [nitems] its flat gradient index, or -1 - q for loss_out[q]
+  int nitems;
+  SlabRuns runs;
+  float scale;
+  float* loss_out;      // [8]
+};
+
+// One optimizer step over a flat range of n parameters (csrc/optim.hip): Adam, the global-norm clip
+// (max_norm > 0) and the refresh of the weight images.
+struct AdamArgs {
+  float* p;
+  float* g;             // the gradient (read; the fused gather + Adam launch writes it)
+  float* m;
+  float* v;
+  int n;
+  float lr, b1, b2, eps;
+  float max_norm;       // <= 0: no clipping (launch_gather_adam: unread)
+  int host_step;        // >= 1: this update's step number (eager launches); 0: the device counter state[1]
+  float* state;         // [4] step counter, staged counter, gradient norm of the clip pass
+  float* norm_part;     // [nblk] per-block sums of squares of the gradient; nblk is the grid
+  int nblk;
+  void* wimg;           // packed weight image in storage precision dt
+  const int* w_map;     // [n] image index of each parameter (-1: none)
+  const int* wt_map;    // [n] index in the transposed image (-1: none)
+  int dt;
+  const float* img_scale;   // optional [n] multiplier of the image values
+  F8Shadow f8;
+  // target_kl (docs/ARCHITECTURE.md §22): null is the ungated launch; else the gated form — gate
+  // f32[4] = [stop, applied, trip_kl, last_kl] is read only, the step number is state[0] + 1 read on
+  // the device (host_step unread), and the launch writes neither state[0] nor state[1]: launch_kl_gate
+  // is the only writer of gate and, in gated mode, of both.  A stopped launch (gate[0] != 0) still
+  // writes the gradient, the loss sums, norm_part and state[2]; p, m, v and the images stay.
+  const float* gate;
+};
+
 struct WgradTask {
   int layer;      // 0..5
   int n0, k0;     // output tile origin
@@ -315,53 +361,27 @@ void set_s3_value_waves(int nw);                // split-bf16 value forward: 4 o
 int mlp_train_waves(int dt, const MlpArgs& a);  // workgroup waves the launcher will use
 void launch_wgrad(int dt, const WgradArgs& a, hipStream_t s);
 int wgrad_task_ok(int dt, int nq, int kq);   // the (nq, kq) quadrant tiles the wgrad kernel runs
-// grad[i] for i in [i_lo, i_hi) from the slabs (src_off / src_meta: see grad_gather_kernel);
-// with_partials: also log_std grads [0, A) and the 8 loss sums from the per-workgroup partials
-void launch_grad_gather(const float* slab, const int* src_off, const int* src_meta, const float* part, int nblk,
-                        int npart, const int* red_col, const int* red_dst, int nitems, float scale, float* grad,
-                        const SlabRuns& runs, float* loss_out, hipStream_t s);
-void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
-                int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s);
-// boot: optional [T][E] value of a truncated step's final observation (null: launch_gae)
-void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot, float* adv,
-                     float* ret, int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s);
+// grad[i] = scale * (slab sum | item column sum) for the gather's elements, loss_out from its items
+void launch_grad_gather(const GatherArgs& ga, float* grad, hipStream_t s);
+// boot: optional [T][E] value of a truncated step's final observation (null: the kernels without it)
 // scale: optional device scalar (reward_norm: r' = clamp(fl32(r * scale), +-rclip), rclip <= 0: no clamp;
-// null: launch_gae_boot)
+// null: the kernels without the reward scaling)
 void launch_gae_rn(const float* rewards, const float* values, const float* dones, const float* boot,
                    const float* scale, float rclip, float* adv, float* ret, int T, int E, float gamma, float lam,
                    int mode, int seg, hipStream_t s);
 // csrc/retnorm.hip: forward scan of the discounted return over [T][E] rewards / dones (acc [E] in place),
-// s12 = the samples' (S1, S2) about shift[0]; mode as launch_gae_boot; R_out optional [T][E] (null: skipped);
+// s12 = the samples' (S1, S2) about shift[0]; mode as launch_gae_rn; R_out optional [T][E] (null: skipped);
 // part: ret_scan_blocks(T, E, mode) x 2 doubles of scratch
 int ret_scan_blocks(int T, int E, int mode);
 void launch_ret_scan(const float* rewards, const float* dones, float* acc, const float* shift, float* R_out,
                      double* part, double* s12, int T, int E, float gamma, int mode, hipStream_t s);
 void set_adam_fused(int on);
-void launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                 float eps, float max_norm, float* state, float* norm_part, int nblk,
-                 void* wimg, const int* w_map, const int* wt_map, int dt, const float* img_scale, int host_step,
-                 const F8Shadow& f8, hipStream_t s);
-// grad_gather (with the partials pass, range [A, n)) + no-clip Adam fused: world size 1 only
-// (no all-reduce between them); nblk = norm_part size, must exceed A + 8
-void launch_gather_adam(const float* slab, const int* src_off, const int* src_meta, const float* part, int npblk,
-                        int npart, const int* red_col, const int* red_dst, int nitems, const SlabRuns& runs,
-                        float scale, float* loss_out, float* g, float* p, float* m, float* v,
-                        int n, float lr, float b1, float b2, float eps, int step, float* state, float* norm_part,
-                        int nblk, void* wimg, const int* w_map, const int* wt_map, int dt, const float* img_scale,
-                        const F8Shadow& f8, hipStream_t s);
-// target_kl (docs/ARCHITECTURE.md §22): the gated forms of the two launches above — gate f32[4] =
-// [stop, applied, trip_kl, last_kl] is read only, the step number is state[0] + 1 read on the
-// device, and neither writes state[0] / state[1] — and the gate itself (the only writer of both)
-void launch_adam_gated(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                       float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
-                       const int* w_map, const int* wt_map, int dt, const float* img_scale, const F8Shadow& f8,
-                       const float* gate, hipStream_t s);
-void launch_gather_adam_gated(const float* slab, const int* src_off, const int* src_meta, const float* part,
-                              int npblk, int npart, const int* red_col, const int* red_dst, int nitems,
-                              const SlabRuns& runs, float scale, float* loss_out, float* g, float* p, float* m,
-                              float* v, int n, float lr, float b1, float b2, float eps, float* state,
-                              float* norm_part, int nblk, void* wimg, const int* w_map, const int* wt_map, int dt,
-                              const float* img_scale, const F8Shadow& f8, const float* gate, hipStream_t s);
+// one launch without clipping when the step number is known (host_step > 0 or gated), else sumsq + adam
+void launch_adam(const AdamArgs& a, hipStream_t s);
+// grad_gather + no-clip Adam in one launch: world size 1 only (no all-reduce between them); a.nblk
+// must exceed item_blocks(ga.nitems), and ungated it needs a.host_step >= 1
+void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipStream_t s);
+// target_kl: the gate after a step (AdamArgs::gate)
 void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s);
 void launch_pack(const float* p, int n, void* wimg, const int* w_map, const int* wt_map, int dt,
                  const float* img_scale, hipStream_t s);

@@ -663,130 +663,54 @@ extern "C" void launch_gae_rn(const float* rewards, const float* values, const f
   }
   HIP_CHECK_LAUNCH();
 }
-extern "C" void launch_gae_boot(const float* rewards, const float* values, const float* dones, const float* boot,
-                                float* adv, float* ret, int T, int E, float gamma, float lam, int mode, int seg,
-                                hipStream_t s) {
-  launch_gae_rn(rewards, values, dones, boot, nullptr, 0.f, adv, ret, T, E, gamma, lam, mode, seg, s);
-}
-extern "C" void launch_gae(const float* rewards, const float* values, const float* dones, float* adv, float* ret,
-                           int T, int E, float gamma, float lam, int mode, int seg, hipStream_t s) {
-  launch_gae_boot(rewards, values, dones, nullptr, adv, ret, T, E, gamma, lam, mode, seg, s);
-}
 
 static int g_adam_fused = 1;   // A/B switch (set_adam_fused): 0 forces the sumsq + adam pair
 extern "C" void set_adam_fused(int on) { g_adam_fused = on; }
 
 namespace {
-template <bool GATE>
-void adam_dispatch(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2, float eps,
-                   float max_norm, float* state, float* norm_part, int nblk, void* wimg, const int* w_map,
-                   const int* wt_map, int dt, const float* img_scale, int host_step, const F8Shadow& f8,
-                   KlGate<GATE> kg, hipStream_t s) {
-  // (GATE: the step number is read on the device, so the one-launch form needs no host step)
-  if (max_norm <= 0.f && g_adam_fused && (GATE || host_step > 0)) {
-    const float step = (float)host_step;
-#define AN_ARGS p, g, m, v, n, lr, b1, b2, eps, step, state, norm_part
-    if (dt == DT_F32)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
-                         (float*)wimg, w_map, wt_map, img_scale, f8, kg);
-    else if (dt == DT_BF16)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
-                         (__bf16*)wimg, w_map, wt_map, img_scale, f8, kg);
-    else if (dt == DT_S3)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
-                         (S3Slot*)wimg, w_map, wt_map, img_scale, f8, kg);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, AN_ARGS,
-                         (uint8_t*)wimg, w_map, wt_map, img_scale, f8, kg);
-#undef AN_ARGS
-    HIP_CHECK_LAUNCH();
-    return;
-  }
-  hipLaunchKernelGGL(sumsq_kernel<GATE>, dim3(nblk), dim3(256), 0, s, g, n, norm_part, state);
-#define AC_ARGS p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk
-  if (dt == DT_F32)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (float*)wimg,
-                       w_map, wt_map, img_scale, f8, kg);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (__bf16*)wimg,
-                       w_map, wt_map, img_scale, f8, kg);
-  else if (dt == DT_S3)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (S3Slot*)wimg,
-                       w_map, wt_map, img_scale, f8, kg);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, AC_ARGS, (uint8_t*)wimg,
-                       w_map, wt_map, img_scale, f8, kg);
-#undef AC_ARGS
-  HIP_CHECK_LAUNCH();
-}
-
-template <bool GATE>
-void gather_adam_dispatch(const float* slab, const int* src_off, const int* src_meta, const float* part, int npblk,
-                          int npart, const int* red_col, const int* red_dst, int nitems, const SlabRuns& runs,
-                          float scale, float* loss_out, float* g, float* p, float* m, float* v, int n, float lr,
-                          float b1, float b2, float eps, int step, float* state, float* norm_part, int nblk,
-                          void* wimg, const int* w_map, const int* wt_map, int dt, const float* img_scale,
-                          const F8Shadow& f8, KlGate<GATE> kg, hipStream_t s) {
-#define GA_ARGS slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale, loss_out, g, p, m, \
-                v, n, lr, b1, b2, eps, \
-                (float)step, state, norm_part
-  if (dt == DT_F32)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_F32, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
-                       (float*)wimg, w_map, wt_map, img_scale, f8, kg);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_BF16, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
-                       (__bf16*)wimg, w_map, wt_map, img_scale, f8, kg);
-  else if (dt == DT_S3)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_S3, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
-                       (S3Slot*)wimg, w_map, wt_map, img_scale, f8, kg);
-  else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT_FP8, GATE>), dim3(nblk), dim3(256), 0, s, GA_ARGS,
-                       (uint8_t*)wimg, w_map, wt_map, img_scale, f8, kg);
-#undef GA_ARGS
-  HIP_CHECK_LAUNCH();
+// f(integral_constant<int, DT>, KlGate<GATE>): the image's precision and, from a.gate, the gated
+// or the ungated form of an Adam launch
+template <typename F>
+void dispatch_adam(const AdamArgs& a, F&& f) {
+  dispatch_dt(a.dt, [&](auto d) {
+    if (a.gate != nullptr) f(d, KlGate<true>{a.gate});
+    else f(d, KlGate<false>{});
+  });
 }
 }  // namespace
 
-extern "C" void launch_adam(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                            float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
-                            const int* w_map, const int* wt_map, int dt, const float* img_scale, int host_step,
-                            const F8Shadow& f8, hipStream_t s) {
-  adam_dispatch<false>(p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk, wimg, w_map, wt_map, dt,
-                       img_scale, host_step, f8, KlGate<false>{}, s);
+extern "C" void launch_adam(const AdamArgs& a, hipStream_t s) {
+  dispatch_adam(a, [&](auto d, auto kg) {
+    constexpr int DT = decltype(d)::value;
+    constexpr bool GATE = std::is_same_v<decltype(kg), KlGate<true>>;
+    auto* wimg = static_cast<typename Prec<DT>::T*>(a.wimg);
+    const dim3 grid(a.nblk), block(256);
+    // (GATE: the step number is read on the device, so the one-launch form needs no host step)
+    if (a.max_norm <= 0.f && g_adam_fused && (GATE || a.host_step > 0)) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_noclip_kernel<DT, GATE>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n,
+                         a.lr, a.b1, a.b2, a.eps, (float)a.host_step, a.state, a.norm_part, wimg, a.w_map, a.wt_map,
+                         a.img_scale, a.f8, kg);
+      return;
+    }
+    hipLaunchKernelGGL(sumsq_kernel<GATE>, grid, block, 0, s, a.g, a.n, a.norm_part, a.state);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(adam_kernel<DT, GATE>), grid, block, 0, s, a.p, a.g, a.m, a.v, a.n, a.lr, a.b1,
+                       a.b2, a.eps, a.max_norm, a.state, a.norm_part, a.nblk, wimg, a.w_map, a.wt_map, a.img_scale,
+                       a.f8, kg);
+  });
+  HIP_CHECK_LAUNCH();
 }
 
-// target_kl: the gated forms (gate f32[4], read only; the step number is state[0] + 1) and the gate
-extern "C" void launch_adam_gated(float* p, const float* g, float* m, float* v, int n, float lr, float b1, float b2,
-                                  float eps, float max_norm, float* state, float* norm_part, int nblk, void* wimg,
-                                  const int* w_map, const int* wt_map, int dt, const float* img_scale,
-                                  const F8Shadow& f8, const float* gate, hipStream_t s) {
-  adam_dispatch<true>(p, g, m, v, n, lr, b1, b2, eps, max_norm, state, norm_part, nblk, wimg, w_map, wt_map, dt,
-                      img_scale, 0, f8, KlGate<true>{gate}, s);
-}
-
-extern "C" void launch_gather_adam(const float* slab, const int* src_off, const int* src_meta, const float* part,
-                                   int npblk, int npart, const int* red_col, const int* red_dst, int nitems,
-                                   const SlabRuns& runs, float scale, float* loss_out, float* g, float* p,
-                                   float* m, float* v, int n, float lr, float b1, float b2, float eps, int step,
-                                   float* state, float* norm_part, int nblk, void* wimg, const int* w_map,
-                                   const int* wt_map, int dt, const float* img_scale, const F8Shadow& f8,
-                                   hipStream_t s) {
-  gather_adam_dispatch<false>(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale,
-                              loss_out, g, p, m, v, n, lr, b1, b2, eps, step, state, norm_part, nblk, wimg, w_map,
-                              wt_map, dt, img_scale, f8, KlGate<false>{}, s);
-}
-
-extern "C" void launch_gather_adam_gated(const float* slab, const int* src_off, const int* src_meta,
-                                         const float* part, int npblk, int npart, const int* red_col,
-                                         const int* red_dst, int nitems, const SlabRuns& runs, float scale,
-                                         float* loss_out, float* g, float* p, float* m, float* v, int n, float lr,
-                                         float b1, float b2, float eps, float* state, float* norm_part, int nblk,
-                                         void* wimg, const int* w_map, const int* wt_map, int dt,
-                                         const float* img_scale, const F8Shadow& f8, const float* gate,
-                                         hipStream_t s) {
-  gather_adam_dispatch<true>(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, nitems, runs, scale,
-                             loss_out, g, p, m, v, n, lr, b1, b2, eps, 0, state, norm_part, nblk, wimg, w_map,
-                             wt_map, dt, img_scale, f8, KlGate<true>{gate}, s);
+extern "C" void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipStream_t s) {
+  dispatch_adam(a, [&](auto d, auto kg) {
+    constexpr int DT = decltype(d)::value;
+    constexpr bool GATE = std::is_same_v<decltype(kg), KlGate<true>>;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT, GATE>), dim3(a.nblk), dim3(256), 0, s, ga.slab,
+                       ga.src_off, ga.src_meta, ga.part, ga.npblk, ga.npart, ga.red_col, ga.red_dst, ga.nitems,
+                       ga.runs, ga.scale, ga.loss_out, a.g, a.p, a.m, a.v, a.n, a.lr, a.b1, a.b2, a.eps,
+                       (float)a.host_step, a.state, a.norm_part, static_cast<typename Prec<DT>::T*>(a.wimg), a.w_map,
+                       a.wt_map, a.img_scale, a.f8, kg);
+  });
+  HIP_CHECK_LAUNCH();
 }
 
 extern "C" void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s) {
@@ -798,13 +722,10 @@ extern "C" void launch_pack(const float* p, int n, void* wimg, const int* w_map,
                             const float* img_scale, hipStream_t s) {
   int grid = (n + 255) / 256;
   if (grid > 1024) grid = 1024;
-  if (dt == DT_F32)
-    hipLaunchKernelGGL(pack_kernel<DT_F32>, dim3(grid), dim3(256), 0, s, p, n, (float*)wimg, w_map, wt_map, img_scale);
-  else if (dt == DT_BF16)
-    hipLaunchKernelGGL(pack_kernel<DT_BF16>, dim3(grid), dim3(256), 0, s, p, n, (__bf16*)wimg, w_map, wt_map, img_scale);
-  else if (dt == DT_S3)
-    hipLaunchKernelGGL(pack_kernel<DT_S3>, dim3(grid), dim3(256), 0, s, p, n, (S3Slot*)wimg, w_map, wt_map, img_scale);
-  else
-    hipLaunchKernelGGL(pack_kernel<DT_FP8>, dim3(grid), dim3(256), 0, s, p, n, (uint8_t*)wimg, w_map, wt_map, img_scale);
+  dispatch_dt(dt, [&](auto d) {
+    constexpr int DT = decltype(d)::value;
+    hipLaunchKernelGGL(pack_kernel<DT>, dim3(grid), dim3(256), 0, s, p, n, static_cast<typename Prec<DT>::T*>(wimg),
+                       w_map, wt_map, img_scale);
+  });
   HIP_CHECK_LAUNCH();
 }

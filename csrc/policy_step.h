@@ -145,14 +145,6 @@ DEV void store_tile_rows(typename Prec<XStore<DT>::DTX>::T* dst, const PolicyTil
   }
 }
 
-// f(integral_constant<int, DT>) for a run-time precision code
-template <typename F>
-auto dispatch_dt(int dt, F&& f) {
-  if (dt == DT_F32) return f(std::integral_constant<int, DT_F32>{});
-  if (dt == DT_BF16) return f(std::integral_constant<int, DT_BF16>{});
-  if (dt == DT_S3) return f(std::integral_constant<int, DT_S3>{});
-  return f(std::integral_constant<int, DT_FP8>{});
-}
 // The kernels' launch form: 8 waves (2 per SIMD: twice the threads of the VALU-heavy observe /
 // sample / env phases) for bf16x3 / bf16 / fp8 16-row tiles, 4 for fp32 operands and 32-row
 // tiles (twice the fragment registers: the 8-wave form spills)

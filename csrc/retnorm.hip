@@ -159,7 +159,7 @@ bool ret_scan_in_time(int T, int E, int mode) { return mode == 2 || (mode == 0 &
 
 extern "C" int ret_scan_blocks(int T, int E, int mode) { return ret_scan_in_time(T, E, mode) ? E : (E + 63) / 64; }
 
-// mode: launch_gae_boot's (0 auto, 1 per-env lanes, 2 parallel in time); R_out: optional [T][E]
+// mode: launch_gae_rn's (0 auto, 1 per-env lanes, 2 parallel in time); R_out: optional [T][E]
 // (null: not written); part: ret_scan_blocks(T, E, mode) x 2 doubles of scratch; s12: [2]
 extern "C" void launch_ret_scan(const float* rewards, const float* dones, float* acc, const float* shift,
                                 float* R_out, double* part, double* s12, int T, int E, float gamma, int mode,

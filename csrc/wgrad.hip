@@ -558,14 +558,12 @@ extern "C" void launch_wgrad(int dt, const WgradArgs& a, hipStream_t s) {
   HIP_CHECK_LAUNCH();
 }
 
-extern "C" void launch_grad_gather(const float* slab, const int* src_off, const int* src_meta, const float* part,
-                                   int nblk, int npart, const int* red_col, const int* red_dst, int nitems,
-                                   float scale, float* grad, const SlabRuns& runs, float* loss_out, hipStream_t s) {
-  int grid = (runs.total + 255) / 256;
+extern "C" void launch_grad_gather(const GatherArgs& ga, float* grad, hipStream_t s) {
+  int grid = (ga.runs.total + 255) / 256;
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
-  grid += item_blocks(nitems);
-  hipLaunchKernelGGL(grad_gather_kernel, dim3(grid), dim3(256), 0, s, slab, src_off, src_meta, part, nblk, npart,
-                     red_col, red_dst, nitems, scale, grad, runs, loss_out);
+  grid += item_blocks(ga.nitems);
+  hipLaunchKernelGGL(grad_gather_kernel, dim3(grid), dim3(256), 0, s, ga.slab, ga.src_off, ga.src_meta, ga.part,
+                     ga.npblk, ga.npart, ga.red_col, ga.red_dst, ga.nitems, ga.scale, grad, ga.runs, ga.loss_out);
   HIP_CHECK_LAUNCH();
 }

@@ -338,6 +338,7 @@ class HipEngine:
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.empty = torch.empty(0, dtype=torch.int32, **dev)
         self.no_q = torch.empty(0, **f32)
+        self._gate_arg = self.no_q if self.gate is None else self.gate    # the Adam bindings' gate (empty: ungated)
         self.no_u8 = torch.empty(0, dtype=torch.uint8, **dev)
         self._first_step = True
         self._loss_dev: Optional[torch.Tensor] = None
@@ -1554,29 +1555,10 @@ class HipEngine:
     def _joint_step(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
         """world size 1: policy kernel, value kernel (one shared partial buffer), ONE wgrad over
         both heads' layers, ONE gather + Adam launch over the whole flat vector"""
-        p, M = self.p, self.mb
         self._joint_heads(idx_t, first, xt_ready, xmode)
         b = self.joint_bucket
         self._wgrad(b, xmode)
-        b1, b2 = p.adam_betas
-        src_off, src_meta = self.joint_src
-        rc, rd = self.items["joint"]
-        if self.gate is not None:       # target_kl: the gated form (step number and stop flag on the device)
-            self.ext.gather_adam_gated(b["slab"], src_off, src_meta, self.part_joint, self.nhead_blk,
-                                       self.part_joint.shape[1], rc, rd, b["runs"], 1.0 / M, self.loss_sums,
-                                       self.grad_flat, self.model.flat.data, self.adam_m, self.adam_v, float(p.lr),
-                                       float(b1), float(b2), float(p.adam_eps), self.adam_state,
-                                       self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map, self.dt,
-                                       self.no_q, *self._f8(), self.gate)
-            self._norm_n = self.norm_n_whole
-            return
-        self.ext.gather_adam(b["slab"], src_off, src_meta, self.part_joint, self.nhead_blk, self.part_joint.shape[1],
-                             rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat, self.model.flat.data,
-                             self.adam_m, self.adam_v, float(p.lr), float(b1), float(b2), float(p.adam_eps),
-                             self.adam_step + 1, self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg,
-                             self.w_map, self.wt_map, self.dt, self.no_q, *self._f8())
-        self.adam_step += 1
-        self._norm_n = self.norm_n_whole
+        self._gather_adam(b, *self.joint_src, self.part_joint, self.nhead_blk, self.items["joint"])
 
     def _head_chain(self, h: int, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
         """head h's kernel -> its wgrad -> its gather into its flat range of grad_flat"""
@@ -1593,14 +1575,42 @@ class HipEngine:
 
     def _head_adam(self, h: int, step_no: int) -> None:
         """no-clip Adam over head h's flat range (after its all-reduce); its norm region"""
-        p = self.p
         lo, hi = self.head_range[h]
         r0, r1 = self.norm_regions[h]
+        self._adam(lo, hi, self.norm_part[r0:r1], 0.0, step_no)
+
+    def _next_step(self) -> int:
+        """the host step number of the next optimizer launch; target_kl: 0, the gated form reads the number
+        (and the stop flag) on the device"""
+        return 0 if self.gate is not None else self.adam_step + 1
+
+    def _stepped(self, norm_n: int) -> None:
+        """books of a whole optimizer step just launched, which left norm_n norm partials"""
+        if self.gate is None:       # (target_kl: kl_gate advances the device counter)
+            self.adam_step += 1
+        self._norm_n = norm_n
+
+    def _adam(self, lo: int, hi: int, norm_part: torch.Tensor, max_norm: float, step_no: int) -> None:
+        """the Adam launch over the flat range [lo, hi): one kernel without clipping when the step number is
+        known (step_no >= 1, or gated), the sumsq + adam pair otherwise"""
+        p = self.p
         b1, b2 = p.adam_betas
         self.ext.adam(self.model.flat.data[lo:hi], self.grad_flat[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi],
-                      float(p.lr), float(b1), float(b2), float(p.adam_eps), 0.0, self.adam_state,
-                      self.norm_part[r0:r1], self.wimg, self.w_map[lo:hi], self.wt_map[lo:hi], self.dt, self.no_q,
-                      step_no, *self._f8(lo, hi))
+                      float(p.lr), float(b1), float(b2), float(p.adam_eps), max_norm, self.adam_state, norm_part,
+                      self.wimg, self.w_map[lo:hi], self.wt_map[lo:hi], self.dt, self.no_q, step_no,
+                      *self._f8(lo, hi), self._gate_arg)
+
+    def _gather_adam(self, b: Dict, src_off: torch.Tensor, src_meta: torch.Tensor, part: torch.Tensor, npblk: int,
+                     items) -> None:
+        """ONE whole optimizer step as the fused gather + no-clip Adam launch over bucket b (world size 1)"""
+        p = self.p
+        b1, b2 = p.adam_betas
+        self.ext.gather_adam(b["slab"], src_off, src_meta, part, npblk, part.shape[1], *items, b["runs"],
+                             1.0 / self.mb, self.loss_sums, self.grad_flat, self.model.flat.data, self.adam_m,
+                             self.adam_v, float(p.lr), float(b1), float(b2), float(p.adam_eps), self._next_step(),
+                             self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map,
+                             self.dt, self.no_q, *self._f8(), self._gate_arg)
+        self._stepped(self.norm_n_whole)
 
     def grad(self, idx: Optional[torch.Tensor], apply: bool = False) -> None:
         """one minibatch gradient into grad_flat (no optimizer step; tests / the whole-vector
@@ -1619,9 +1629,6 @@ class HipEngine:
         if apply:
             assert self.can_fuse_apply(), "fused gather + Adam is not available here"
             self._launch_grad(idx_t, first, xt_ready, fused_apply=True)
-            if self.gate is None:       # (target_kl: kl_gate advances the device counter)
-                self.adam_step += 1
-            self._norm_n = self.norm_n_whole
         else:
             self._launch_grad(idx_t, first, xt_ready)
         return None
@@ -1640,22 +1647,7 @@ class HipEngine:
         if fused_apply:
             if p.loss == "dppo_ref":   # train.py:164: the pre-update log_std, before Adam moves it
                 self.log_std_old.copy_(self.model.flat.data[:self.A])
-            b1, b2 = p.adam_betas
-            rc, rd = self.items["legacy"]
-            if self.gate is not None:   # target_kl: the gated form
-                self.ext.gather_adam_gated(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk,
-                                           self.npart, rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat,
-                                           self.model.flat.data, self.adam_m, self.adam_v, float(p.lr), float(b1),
-                                           float(b2), float(p.adam_eps), self.adam_state,
-                                           self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map,
-                                           self.dt, self.no_q, *self._f8(), self.gate)
-                return
-            self.ext.gather_adam(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk,
-                                 self.npart, rc, rd, b["runs"], 1.0 / M, self.loss_sums, self.grad_flat,
-                                 self.model.flat.data, self.adam_m, self.adam_v, float(p.lr), float(b1),
-                                 float(b2), float(p.adam_eps), self.adam_step + 1, self.adam_state,
-                                 self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map, self.dt,
-                                 self.no_q, *self._f8())
+            self._gather_adam(b, self.src_off, self.src_meta, self.part, self.ntrain_blk, self.items["legacy"])
             return
         rc, rd = self.items["legacy"]
         self.ext.grad_gather(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk, self.npart,
@@ -1671,22 +1663,8 @@ class HipEngine:
         if extra_grad:
             self.grad_flat.add_(extra_grad)
         mx = float(p.max_grad_norm) if (p.max_grad_norm is not None and p.max_grad_norm > 0) else 0.0
-        b1, b2 = p.adam_betas
-        if self.gate is not None:
-            # target_kl: the gated form — one launch without clipping, the sumsq + adam pair with it;
-            # the step number and the stop flag are read on the device, kl_gate advances the counter
-            self.ext.adam_gated(self.model.flat.data, self.grad_flat, self.adam_m, self.adam_v, float(p.lr), float(b1),
-                                float(b2), float(p.adam_eps), mx, self.adam_state, self.norm_part[:self.norm_n_whole],
-                                self.wimg, self.w_map, self.wt_map, self.dt, self.no_q, *self._f8(), self.gate)
-            self._norm_n = self.norm_n_whole
-            return None
-        # the host knows the step number: one fused kernel without clipping
-        self.ext.adam(self.model.flat.data, self.grad_flat, self.adam_m, self.adam_v, float(p.lr), float(b1),
-                      float(b2), float(p.adam_eps), mx, self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg,
-                      self.w_map, self.wt_map, self.dt, self.no_q, self.adam_step + 1, *self._f8())
-        self.adam_step += 1
-        self._norm_n = self.norm_n_whole
-        return None
+        self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_whole], mx, self._next_step())
+        self._stepped(self.norm_n_whole)
 
     def pack_metrics(self, ep2: torch.Tensor) -> Optional[torch.Tensor]:
         """device f64[11] = [episode return sum, count | loss sums (8) | grad norm], written by ONE

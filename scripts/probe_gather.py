@@ -22,21 +22,15 @@ def main():
     w = DPPOWorker(p, DistContext(device=dev))
     w.iteration_step()
     eng = w.engine
-    ext = eng.ext
     b = eng.joint_bucket
-    src_off, src_meta = eng.joint_src
     rc, rd = eng.items["joint"]
-    b1, b2 = p.adam_betas
     n = eng.model.num_params
     empty_i = torch.empty(0, dtype=torch.int32, device=dev)
+    eng.p.lr = 0.0          # (the launches of the window leave the parameters where they are)
 
     def run(items, runs):
-        c, d = (rc, rd) if items else (empty_i, empty_i)
-        ext.gather_adam(b["slab"], src_off, src_meta, eng.part_joint, eng.nhead_blk, eng.part_joint.shape[1], c, d,
-                        runs, 1.0 / eng.mb, eng.loss_sums, eng.grad_flat, eng.model.flat.data, eng.adam_m,
-                        eng.adam_v, 0.0, float(b1), float(b2), float(p.adam_eps), 1, eng.adam_state,
-                        eng.norm_part[:eng.norm_n_whole], eng.wimg, eng.w_map, eng.wt_map, eng.dt, eng.no_q,
-                        *eng._f8())
+        eng._gather_adam(dict(b, runs=runs), *eng.joint_src, eng.part_joint, eng.nhead_blk,
+                         (rc, rd) if items else (empty_i, empty_i))
     arms = {"full": (True, b["runs"]), "items_only": (True, [n, n]), "slab_only": (False, b["runs"])}
     res = {}
     for name, (items, runs) in arms.items():

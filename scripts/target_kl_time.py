@@ -51,19 +51,9 @@ def build(dev, target_kl):
 
 
 def gather_adam(eng):
-    """the joint gather + Adam launch of HipEngine._joint_step, alone"""
-    p, b = eng.p, eng.joint_bucket
-    b1, b2 = p.adam_betas
-    src_off, src_meta = eng.joint_src
-    rc, rd = eng.items["joint"]
-    head = (b["slab"], src_off, src_meta, eng.part_joint, eng.nhead_blk, eng.part_joint.shape[1], rc, rd, b["runs"],
-            1.0 / eng.mb, eng.loss_sums, eng.grad_flat, eng.model.flat.data, eng.adam_m, eng.adam_v, float(p.lr),
-            float(b1), float(b2), float(p.adam_eps))
-    tail = (eng.adam_state, eng.norm_part[:eng.norm_n_whole], eng.wimg, eng.w_map, eng.wt_map, eng.dt, eng.no_q,
-            *eng._f8())
-    if eng.gate is not None:
-        return lambda: eng.ext.gather_adam_gated(*head, *tail, eng.gate)
-    return lambda: eng.ext.gather_adam(*head, 2, *tail)
+    """the joint gather + Adam launch of HipEngine._joint_step, alone (ungated: the host counts every launch)"""
+    return lambda: eng._gather_adam(eng.joint_bucket, *eng.joint_src, eng.part_joint, eng.nhead_blk,
+                                    eng.items["joint"])
 
 
 def window_us(fn, reps):

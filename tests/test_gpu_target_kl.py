@@ -127,6 +127,51 @@ def test_kl_gate_binding_refusals():
     torch.cuda.synchronize()
 
 
+def test_adam_binding_gate_argument_and_refusals():
+    """``adam`` / ``gather_adam`` on a flat vector of 300 parameters with an fp32 image nobody is mapped into: an
+    empty gate is the ungated launch (which counts the step), a well-formed gate the gated one (the counter belongs
+    to kl_gate), and a malformed gate — or no gate and no host step number for the fused launch — raises before
+    anything is launched."""
+    ext, n = _ext(), 300
+    f32, i32 = dict(dtype=torch.float32, device=DEV), dict(dtype=torch.int32, device=DEV)
+    gen = torch.Generator().manual_seed(5)
+    p0 = torch.randn(n, generator=gen).to(DEV)
+    p, g, m, v = p0.clone(), torch.randn(n, generator=gen).to(DEV), torch.zeros(n, **f32), torch.zeros(n, **f32)
+    state, wimg, no_map = torch.zeros(4, **f32), torch.zeros(32, **f32), torch.full((n,), -1, **i32)
+    no_q, no_i, no_u8 = torch.empty(0, **f32), torch.empty(0, **i32), torch.empty(0, dtype=torch.uint8, device=DEV)
+
+    def adam(gate, host_step, max_norm, nblk):
+        ext.adam(p, g, m, v, 1e-3, 0.9, 0.999, 1e-8, max_norm, state, torch.zeros(nblk, **f32), wimg, no_map, no_map,
+                 0, no_q, host_step, no_u8, no_i, no_q, gate)
+
+    def gather_adam(gate, step):
+        # one reduce item (partial column 0 -> loss_out[0]) and one slab run: every element is slab[0], one chunk
+        ext.gather_adam(torch.ones(1, **f32), torch.zeros(n, **i32), torch.full((n,), 32, **i32), torch.ones(1, **f32),
+                        1, 1, torch.zeros(1, **i32), torch.full((1,), -1, **i32), [0, n], 1.0, torch.zeros(8, **f32),
+                        g, p, m, v, 1e-3, 0.9, 0.999, 1e-8, step, state, torch.zeros(2, **f32), wimg, no_map, no_map,
+                        0, no_q, no_u8, no_i, no_q, gate)
+
+    adam(no_q, 1, 0.0, 1)                      # ungated, no clipping: one launch, which writes the counter
+    torch.cuda.synchronize()
+    assert state.tolist()[0] == 1.0 and not torch.equal(p, p0)
+    p1 = p.clone()
+    adam(torch.zeros(4, **f32), 0, 0.5, 2)     # gated and open: applied, the counter is left to kl_gate
+    torch.cuda.synchronize()
+    assert state.tolist()[:2] == [1.0, 1.0] and not torch.equal(p, p1)
+    p2 = p.clone()
+    bad = (torch.zeros(3, **f32), torch.zeros(5, **f32), torch.zeros(4, dtype=torch.float64, device=DEV),
+           torch.zeros(4))
+    for gate in bad:
+        with pytest.raises(RuntimeError, match="gate"):
+            adam(gate, 1, 0.0, 1)
+        with pytest.raises(RuntimeError, match="gate"):
+            gather_adam(gate, 1)
+    with pytest.raises(RuntimeError, match="host step number"):
+        gather_adam(no_q, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(p, p2) and state.tolist()[:2] == [1.0, 1.0]
+
+
 # ---- the gated Adam forms --------------------------------------------------------------------------------------
 PATHS = {"joint": dict(update_kernels="heads"), "unfused": dict(update_kernels="heads", fused_apply=False),
          "tile": dict(update_kernels="tile"), "tile_unfused": dict(update_kernels="tile", fused_apply=False),
