@@ -59,7 +59,10 @@ at::ScalarType storage_type(int dt) {
   return dt == 0 ? at::kFloat : (dt == 1 ? at::kBFloat16 : (dt == 3 ? at::kInt : at::kByte));
 }
 
-void check(const torch::Tensor& t, const char* name, at::ScalarType st, int64_t min_numel) {
+using CT = const torch::Tensor&;
+using Ints = const std::vector<int64_t>&;
+
+void check(CT t, const char* name, at::ScalarType st, int64_t min_numel) {
   TORCH_CHECK(t.is_cuda(), name, " must be a device tensor");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
   TORCH_CHECK(t.scalar_type() == st, name, " has dtype ", t.scalar_type(), ", expected ", st);
@@ -118,26 +121,37 @@ PolicyNet policy_net(int64_t dt, const Layout& L, const torch::Tensor& wimg, con
   return n;
 }
 
-// ------------------------------------------------------------------------------------------
-RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
-                         torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
-                         torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor x_out,
-                         torch::Tensor actions, torch::Tensor logp, torch::Tensor rewards, torch::Tensor dones,
-                         torch::Tensor mom, torch::Tensor epstat, std::vector<int64_t> ints, std::vector<int64_t> keys,
-                         double reward_clip, torch::Tensor qscale, torch::Tensor xT_out, int64_t xT_rows) {
-  TORCH_CHECK(ints.size() == 11, "ints: kind,E,O,A,S,T,t_base,buf_E,t0,limit,std_var");
+// The env fields RolloutArgs and EvalArgs share (ints kind,E,O,A,S lead both bindings' lists): the env kind
+// against its state / observation / action dims (O, A >= 1) and the layout, and the four stream keys
+template <class Args> void check_env(const Args& a, const Layout& L) {
+  TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
+  TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
+  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
+              "state dims");
+  TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
+}
+template <class Args> void env_keys(Args& a, Ints keys) {
   TORCH_CHECK(keys.size() == 4, "keys: env,term,reset,action");
+  a.key_env = (uint32_t)keys[0]; a.key_term = (uint32_t)keys[1]; a.key_reset = (uint32_t)keys[2];
+  a.key_action = (uint32_t)keys[3];
+}
+
+// ------------------------------------------------------------------------------------------
+// RolloutArgs of a rollout launch, checked: the parameter list of ext.rollout, which rollout_fin extends
+RolloutArgs rollout_args(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_ret, CT wimg, Ints layout,
+                         const std::vector<double>& scales, CT flat, CT mean, CT inv_std, CT shift, CT x_out, CT actions,
+                         CT logp, CT rewards, CT dones, CT mom, CT epstat, Ints ints, Ints keys, double reward_clip,
+                         CT qscale, CT xT_out, int64_t xT_rows) {
+  TORCH_CHECK(ints.size() == 11, "ints: kind,E,O,A,S,T,t_base,buf_E,t0,limit,std_var");
+  RolloutArgs a{};
+  env_keys(a, keys);
   TORCH_CHECK(rows == 16 || rows == 32, "rows must be 16 or 32");
   Layout L = parse_layout(layout);
-  RolloutArgs a{};
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.T = (int)ints[5]; a.t_base = (int)ints[6]; a.buf_E = (int)ints[7]; a.t0 = (uint32_t)ints[8];
   a.limit = (int)ints[9];
   TORCH_CHECK(a.E > 0 && a.T >= 1 && a.buf_E == a.E, "bad E/T");
-  TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
-  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
-              "state dims");
-  TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
+  check_env(a, L);
   const int nblk = (a.E + (int)rows - 1) / (int)rows;
   check(state, "state", at::kFloat, (int64_t)a.E * a.S);
   check(ep_len, "ep_len", at::kInt, a.E);
@@ -154,8 +168,6 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   check(dones, "dones", at::kFloat, (int64_t)(a.t_base + a.T) * a.E);
   check(mom, "mom", at::kFloat, (int64_t)nblk * 2 * a.O);
   check(epstat, "epstat", at::kFloat, (int64_t)nblk * 2);
-  a.key_env = (uint32_t)keys[0]; a.key_term = (uint32_t)keys[1]; a.key_reset = (uint32_t)keys[2];
-  a.key_action = (uint32_t)keys[3];
   a.state = state.data_ptr<float>();
   a.ep_len = ep_len.data_ptr<int>();
   a.ep_ret = ep_ret.data_ptr<float>();
@@ -189,58 +201,46 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, torch::Tensor state, torch::T
   return a;
 }
 
-void rollout(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
-             torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
-             torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor x_out,
-             torch::Tensor actions, torch::Tensor logp, torch::Tensor rewards, torch::Tensor dones,
-             torch::Tensor mom, torch::Tensor epstat, std::vector<int64_t> ints, std::vector<int64_t> keys,
-             double reward_clip, torch::Tensor qscale, torch::Tensor xT_out, int64_t xT_rows) {
-  RolloutArgs a = rollout_args(dt, rows, state, ep_len, ep_ret, wimg, layout, scales, flat, mean, inv_std, shift,
-                               x_out, actions, logp, rewards, dones, mom, epstat, ints, keys, reward_clip, qscale,
-                               xT_out, xT_rows);
-  launch_rollout((int)dt, a, (int)rows, cur_stream());
-  after_launch(__func__);
-}
-
-// rollout() with bootstrap_time_limit's outputs (csrc/rollout.hip FIN): trunc [t_base + T][E] fp32
+// ext.rollout and ext.rollout_fin: rollout_args' parameters (the pack P, deduced from it) and one body.
+// rollout_fin adds bootstrap_time_limit's outputs (csrc/rollout.hip FIN): trunc [t_base + T][E] fp32
 // gets 1 where an episode ended by the step limit alone, and x_fin [fin_K][E][d1] (x_out's storage
 // type, zeroed by the caller) the normalised observation such a step reached before its reset, at
 // row ((t_base + step) / limit) * E + e.  Every extent the kernel indexes is checked here.
-void rollout_fin(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
-                 torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
-                 torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor x_out,
-                 torch::Tensor actions, torch::Tensor logp, torch::Tensor rewards, torch::Tensor dones,
-                 torch::Tensor mom, torch::Tensor epstat, std::vector<int64_t> ints, std::vector<int64_t> keys,
-                 double reward_clip, torch::Tensor qscale, torch::Tensor xT_out, int64_t xT_rows, torch::Tensor trunc,
-                 torch::Tensor x_fin, int64_t fin_K) {
-  RolloutArgs a = rollout_args(dt, rows, state, ep_len, ep_ret, wimg, layout, scales, flat, mean, inv_std, shift,
-                               x_out, actions, logp, rewards, dones, mom, epstat, ints, keys, reward_clip, qscale,
-                               xT_out, xT_rows);
-  TORCH_CHECK(a.limit >= 1, "limit must be >= 1, got ", a.limit);
-  const int64_t steps = (int64_t)a.t_base + a.T;
-  TORCH_CHECK(fin_K >= 1 && fin_K <= std::numeric_limits<int>::max() && fin_K >= (steps + a.limit - 1) / a.limit,
-              "fin_K = ", fin_K, " is below ceil(T / limit) = ", (steps + a.limit - 1) / a.limit);
-  check(trunc, "trunc", at::kFloat, steps * a.E);
-  check(x_fin, "x_fin", storage_type(dt == 2 ? 1 : (int)dt), fin_K * a.E * a.net.d1);
-  a.trunc = trunc.data_ptr<float>();
-  a.x_fin = x_fin.data_ptr();
-  a.fin_K = (int)fin_K;
-  launch_rollout((int)dt, a, (int)rows, cur_stream());
-  after_launch(__func__);
-}
+template <class F> struct RolloutBind;
+template <class... P> struct RolloutBind<RolloutArgs (*)(int64_t, int64_t, P...)> {
+  static void run(const char* who, bool fin, CT trunc, CT x_fin, int64_t fin_K, int64_t dt, int64_t rows, P... p) {
+    RolloutArgs a = rollout_args(dt, rows, p...);
+    if (fin) {
+      TORCH_CHECK(a.limit >= 1, "limit must be >= 1, got ", a.limit);
+      const int64_t steps = (int64_t)a.t_base + a.T;
+      TORCH_CHECK(fin_K >= 1 && fin_K <= std::numeric_limits<int>::max() && fin_K >= (steps + a.limit - 1) / a.limit,
+                  "fin_K = ", fin_K, " is below ceil(T / limit) = ", (steps + a.limit - 1) / a.limit);
+      check(trunc, "trunc", at::kFloat, steps * a.E);
+      check(x_fin, "x_fin", storage_type(dt == 2 ? 1 : (int)dt), fin_K * a.E * a.net.d1);
+      a.trunc = trunc.data_ptr<float>();
+      a.x_fin = x_fin.data_ptr();
+      a.fin_K = (int)fin_K;
+    }
+    launch_rollout((int)dt, a, (int)rows, cur_stream());
+    after_launch(who);
+  }
+  static void rollout(int64_t dt, int64_t rows, P... p) { run(__func__, false, {}, {}, 0, dt, rows, p...); }
+  static void rollout_fin(int64_t dt, int64_t rows, P... p, torch::Tensor trunc, torch::Tensor x_fin, int64_t fin_K) {
+    run(__func__, true, trunc, x_fin, fin_K, dt, rows, p...);
+  }
+};
+using RolloutB = RolloutBind<decltype(&rollout_args)>;
 
 // The per-step observation-normalisation rollout (obs_norm_update = "step") as ONE cooperative
 // launch (csrc/rollout.hip sn_step): `sn` = [mean f64, m2 f64, mean_f32, inv_std] of the stats the
 // steps absorb (updated in place), g1 / g2 the granule buffers (int64, zero-initialised once; tags
 // never reused: epoch0 grows by T per launch), err an int32 timeout word.  The launch's own
 // normalisation inputs (mean / inv_std) are ignored: every step takes the freshly merged stats.
-void rollout_stepnorm(int64_t dt, int64_t rows, torch::Tensor state, torch::Tensor ep_len, torch::Tensor ep_ret,
-                      torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat,
-                      torch::Tensor shift, torch::Tensor x_out, torch::Tensor actions, torch::Tensor logp,
-                      torch::Tensor rewards, torch::Tensor dones, torch::Tensor mom, torch::Tensor epstat,
-                      std::vector<int64_t> ints, std::vector<int64_t> keys, double reward_clip, torch::Tensor qscale,
-                      std::vector<torch::Tensor> sn, torch::Tensor g1, torch::Tensor g2, torch::Tensor err,
-                      double n0, int64_t epoch0, double var_floor) {
+void rollout_stepnorm(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_ret, CT wimg, Ints layout,
+                      const std::vector<double>& scales, CT flat, CT shift, CT x_out, CT actions, CT logp, CT rewards,
+                      CT dones, CT mom, CT epstat, Ints ints, Ints keys, double reward_clip, CT qscale,
+                      const std::vector<torch::Tensor>& sn, CT g1, CT g2, CT err, double n0, int64_t epoch0,
+                      double var_floor) {
   TORCH_CHECK(sn.size() == 4, "sn: mean f64, m2 f64, mean_f32, inv_std");
   RolloutArgs a = rollout_args(dt, rows, state, ep_len, ep_ret, wimg, layout, scales, flat, sn[2], sn[3], shift,
                                x_out, actions, logp, rewards, dones, mom, epstat, ints, keys, reward_clip, qscale,
@@ -276,19 +276,15 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
                   std::vector<int64_t> ints, std::vector<int64_t> keys, torch::Tensor qscale) {
   TORCH_CHECK(dt >= 0 && dt <= 3, "dt");
   TORCH_CHECK(ints.size() == 8, "ints: kind,E,O,A,S,limit,std_var,deterministic");
-  TORCH_CHECK(keys.size() == 4, "keys: env,term,reset,action");
+  EvalArgs a{};
+  env_keys(a, keys);
   TORCH_CHECK(scales.size() >= 3, "scales");
   Layout L = parse_layout(layout);
-  EvalArgs a{};
   TORCH_CHECK(ints[1] > 0 && ints[1] <= (int64_t)1 << 30, "E must be in [1, 2^30], got ", ints[1]);
   TORCH_CHECK(ints[5] >= 1 && ints[5] <= (int64_t)1 << 20, "limit must be in [1, 2^20], got ", ints[5]);
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.limit = (int)ints[5]; a.deterministic = ints[7] ? 1 : 0;
-  TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
-  TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
-  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
-              "state dims");
-  TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
+  check_env(a, L);
   a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[6] ? 1 : 0, qscale);
   check(mean, "mean", at::kFloat, a.O);
   check(inv_std, "inv_std", at::kFloat, a.O);
@@ -296,8 +292,6 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
   check(len, "len", at::kInt, a.E);
   TORCH_CHECK(ret.numel() == a.E && len.numel() == a.E, "ret / len must have exactly E = ", a.E, " elements, got ",
               ret.numel(), " / ", len.numel());
-  a.key_env = (uint32_t)keys[0]; a.key_term = (uint32_t)keys[1]; a.key_reset = (uint32_t)keys[2];
-  a.key_action = (uint32_t)keys[3];
   a.mean = mean.data_ptr<float>();
   a.inv_std = inv_std.data_ptr<float>();
   a.ret = ret.data_ptr<float>();
@@ -805,8 +799,6 @@ SlabRuns make_runs(const std::vector<int64_t>& v, int64_t n) {
   return r;
 }
 
-using CT = const torch::Tensor&;
-
 // GatherArgs (csrc/kernels.h) of a gather over a flat range of n elements, checked
 GatherArgs gather_args(CT slab, CT src_off, CT src_meta, CT part, int64_t npblk, int64_t npart, CT red_col, CT red_dst,
                        const std::vector<int64_t>& runs, double scale, CT loss_out, int64_t n) {
@@ -1141,8 +1133,8 @@ void register_comm(pybind11::module& m);   // csrc/comm.cpp: native RCCL communi
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X-native DPPO kernels (gfx950 HIP)";
   register_comm(m);
-  m.def("rollout", &rollout);
-  m.def("rollout_fin", &rollout_fin);
+  m.def("rollout", &RolloutB::rollout);
+  m.def("rollout_fin", &RolloutB::rollout_fin);
   m.def("rollout_stepnorm", &rollout_stepnorm);
   m.def("eval_rollout", &eval_rollout);
   m.def("policy_act", &policy_act);

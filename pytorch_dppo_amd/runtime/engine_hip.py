@@ -336,6 +336,7 @@ class HipEngine:
         self.fused_apply = bool(params.fused_apply)
         self.idx_dev = torch.zeros(self.ldT, dtype=torch.int32, **dev)
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
+        self.std_var = 1 if params.std_convention == "var" else 0   # the policy launches' log_std flag
         self.empty = torch.empty(0, dtype=torch.int32, **dev)
         self.no_q = torch.empty(0, **f32)
         self._gate_arg = self.no_q if self.gate is None else self.gate    # the Adam bindings' gate (empty: ungated)
@@ -753,21 +754,31 @@ class HipEngine:
     def _launch_rollout(self, T: int, t_base: int, t0: int, norm: RunningObsStats, shift: torch.Tensor,
                         xT: Optional[torch.Tensor] = None, mom: Optional[torch.Tensor] = None,
                         epstat: Optional[torch.Tensor] = None):
-        e = self.env
-        kp = e.kernel_params()
-        ints = [self._kind(), self.E, self.O, self.A, e.state_dim, T, t_base, self.E, t0 & 0xFFFFFFFF,
-                kp["limit"], 1 if self.p.std_convention == "var" else 0]
-        keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
-        xt = xT if xT is not None else self.empty_x
-        args = (self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout,
-                self.scales, self.model.flat.data, norm.mean_f32, norm.inv_std_f32, shift, self.x_buf,
-                self.actions, self.logp, self.rewards, self.dones,
-                self.mom if mom is None else mom, self.epstat if epstat is None else epstat, ints, keys,
-                float(self.p.reward_clip), self.qscale, xt, self.x_rows[0])
+        head, tail = self._rollout_args(T, t_base, t0, shift, mom, epstat)
+        args = (*head, norm.mean_f32, norm.inv_std_f32, *tail, self.empty_x if xT is None else xT, self.x_rows[0])
         if self.boot:
             self.ext.rollout_fin(*args, self.trunc, self.x_fin, self.fin_K)
         else:
             self.ext.rollout(*args)
+
+    def _rollout_args(self, T: int, t_base: int, t0: int, shift: torch.Tensor, mom: Optional[torch.Tensor] = None,
+                      epstat: Optional[torch.Tensor] = None):
+        """The positional arguments every rollout binding shares, as (head, tail): ext.rollout /
+        rollout_fin take (*head, mean_f32, inv_std_f32, *tail, xT, xT rows[, trunc, x_fin, fin_K]),
+        ext.rollout_stepnorm (*head, *tail, its stats and granule buffers).
+        ints = [env kind, E, O, A, state dim, steps T of this launch, its first buffer step t_base, the
+        buffer's envs per step (E), step key t0 of its first step (32 bits), episode step limit, std_var];
+        keys = [env, terminal, reset, action]."""
+        e = self.env
+        kp = e.kernel_params()
+        ints = [self._kind(), self.E, self.O, self.A, e.state_dim, T, t_base, self.E, t0 & 0xFFFFFFFF,
+                kp["limit"], self.std_var]
+        keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
+        return ((self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout, self.scales,
+                 self.model.flat.data),
+                (shift, self.x_buf, self.actions, self.logp, self.rewards, self.dones,
+                 self.mom if mom is None else mom, self.epstat if epstat is None else epstat, ints, keys,
+                 float(self.p.reward_clip), self.qscale))
 
     def _kind(self) -> int:
         """the in-kernel env kind of the rollout / eval launches; an env that has none never gets here
@@ -799,17 +810,9 @@ class HipEngine:
         g1, g2, err, err_host = self._sn_bufs
         if int(err_host[0]) != 0:   # (staged after an earlier launch: no sync here)
             raise RuntimeError("per-step observation normalisation launch timed out waiting for a workgroup")
-        e = self.env
-        kp = e.kernel_params()
-        ints = [self._kind(), self.E, self.O, self.A, e.state_dim, self.T, 0, self.E, e.t & 0xFFFFFFFF,
-                kp["limit"], 1 if self.p.std_convention == "var" else 0]
-        keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
-        self.ext.rollout_stepnorm(self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout,
-                                  self.scales, self.model.flat.data, shift, self.x_buf, self.actions, self.logp,
-                                  self.rewards, self.dones, self.mom, self.epstat, ints, keys,
-                                  float(self.p.reward_clip), self.qscale,
-                                  [ls.mean, ls.mean_diff, ls.mean_f32, ls.inv_std_f32], g1, g2, err, float(ls.n),
-                                  self._sn_epoch, 1e-2)
+        head, tail = self._rollout_args(self.T, 0, self.env.t, shift)
+        self.ext.rollout_stepnorm(*head, *tail, [ls.mean, ls.mean_diff, ls.mean_f32, ls.inv_std_f32], g1, g2, err,
+                                  float(ls.n), self._sn_epoch, 1e-2)
         self._sn_epoch += self.T
         ls.n += float(self.N)
         err_host.copy_(err, non_blocking=True)
@@ -854,15 +857,10 @@ class HipEngine:
         if self.p.host_policy == "kernel":
             return self._rollout_host_kernel()
         p, T, E, O = self.p, self.T, self.E, self.O
-        shift = self.stats.shift().clone()
+        norm, shift = self._rollout_begin()
         s1 = torch.zeros(O, dtype=torch.float64, device=self.device)
         s2 = torch.zeros_like(s1)
         ep = torch.zeros(2, dtype=torch.float64, device=self.device)
-        norm = self.stats
-        if p.obs_norm_update == "step":
-            self.local_stats = RunningObsStats(O, self.device)
-            self.local_stats.copy_from(self.stats)
-            norm = self.local_stats
         log_std = self.model.view("log_std")
         log_sigma = log_std if p.std_convention == "std" else 0.5 * log_std
         sigma = torch.exp(log_sigma)
@@ -899,54 +897,84 @@ class HipEngine:
         self._host_obs = obs
         self.x_buf.copy_(self.encode(X.view(-1, self.d0)))
         self._xT_valid = False
-        return {"count": float(self.N), "s1": s1, "s2": s2, "shift": shift,
+        return self._rollout_result(shift, (s1, s2), ep)
+
+    def _rollout_begin(self, snapshot: bool = True):
+        """(norm, shift) of a rollout: the stats that normalise its observations and the shift its
+        moments are taken about.  obs_norm_update = "step": a fresh worker-local copy of the stats
+        (``local_stats``), which every step's batch is merged into before it is normalised."""
+        # a snapshot of the fp32 mean: always in step mode and on the host paths; the device-stepped
+        # path in rollout mode passes the live mean itself, as the fused path does (no copy)
+        shift = self.stats.shift().clone() if snapshot or self.p.obs_norm_update == "step" else self.stats.shift()
+        if self.p.obs_norm_update != "step":
+            return self.stats, shift
+        self.local_stats = RunningObsStats(self.O, self.device)
+        self.local_stats.copy_from(self.stats)
+        return self.local_stats, shift
+
+    def _rollout_result(self, shift: torch.Tensor, s12, ep: torch.Tensor) -> Dict:
+        """what every rollout path returns: the moments (S1, S2) of its N observations about ``shift``
+        and the fp64 [return sum, count] of the episodes it ended, all on the device"""
+        return {"count": float(self.N), "s1": s12[0], "s2": s12[1], "shift": shift,
                 "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
 
-    @torch.no_grad()
-    def _rollout_host_kernel(self) -> Dict:
-        """_rollout_host with Params.host_policy = "kernel": per env step ONE csrc/act.hip launch
-        normalises the E observations, evaluates the policy on MFMA, samples with the keyed RNG and
-        writes actions / logp and the x_buf rows directly in storage precision, accumulating the
-        moments in ``self.mom``; then the host env step.  After the loop a rows-only launch writes
-        the bootstrap rows and one obs_reduce turns the moments into ``self.s12``.  No fp32 staging
-        tensor, no encode copy, no per-step torch moments / normalise / model / RNG ops."""
-        p, T, E, O = self.p, self.T, self.E, self.O
-        shift = self.stats.shift().clone()
-        # the host envs' episode sums stay in their own tensor: obs_reduce rewrites ep_sum from epstat
-        ep_ret, ep_cnt = 0.0, 0.0
-        norm = self.stats
-        if p.obs_norm_update == "step":
-            self.local_stats = RunningObsStats(O, self.device)
-            self.local_stats.copy_from(self.stats)
-            norm = self.local_stats
-        none = self.no_q
-        obs = self._host_obs.to(self.device, torch.float32).contiguous()
+    def _rollout_steps(self, obs: torch.Tensor, norm: RunningObsStats, shift: torch.Tensor, advance, host_sums=None):
+        """The per-step loop of the stepped rollouts (_rollout_host_kernel, rollout_stepped).  Per env
+        step, on the current stream and with no host sync of its own: in step mode the three
+        obs_observe launches (_observe_step), then ONE csrc/act.hip launch that normalises ``obs``,
+        evaluates the policy on MFMA, samples with the keyed RNG (step key ``env.t``, ``e_base`` 0,
+        the engine's action key: the fused kernel's keys) and writes the step's ``actions`` / ``logp``
+        / ``x_buf`` rows and the moments in ``self.mom``; then ``advance(t, rows, actions, key)``
+        steps the env, fills the step's ``rewards`` / ``dones`` rows and returns the next observation
+        (fp32, contiguous, on the device).  After the loop a rows-only launch writes the bootstrap
+        rows and one obs_reduce turns the moments into ``self.s12`` (and ``epstat`` into ``ep_sum``).
+        ``host_sums``: the host path's [return sum, count] list, which its ``advance`` adds to.
+        Returns (the last observation, the rollout's result dict)."""
+        T, E, env, none = self.T, self.E, self.env, self.no_q
+        step = self.p.obs_norm_update == "step"
         for t in range(T):
-            if p.obs_norm_update == "step":
+            if step:
                 self._observe_step(norm, obs, shift)
             rows = slice(t * E, (t + 1) * E)
             a = self.actions[rows]
-            self._launch_act(obs, self.env.t, False, 0, self.key_action, norm, shift, a, self.logp[rows], none,
+            # step key: the host path's env.t as it is, the device path's 32 bits that its dynamics take too
+            k = env.t if host_sums is not None else env.t & rng.MASK32
+            self._launch_act(obs, k, False, 0, self.key_action, norm, shift, a, self.logp[rows], none,
                              self.x_buf[rows], self.mom, t == 0)
+            obs = advance(t, rows, a, k)
+        # episode sums: the host envs' in an fp64 tensor of their own (obs_reduce rewrites ep_sum from an
+        # epstat that the host path never fills); the device paths' are env_advance's epstat, reduced into ep_sum
+        ep = self.ep_sum if host_sums is None else torch.tensor(host_sums, dtype=torch.float64, device=self.device)
+        # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
+        self._launch_act(obs, env.t, False, 0, self.key_action, norm, shift, none, none, none, self.x_buf[T * E:],
+                         none, False)
+        self._xT_valid = False
+        self.ext.obs_reduce(self.mom, self.mom.shape[0], self.O, self.s12, self.epstat, self.ep_sum)
+        return obs, self._rollout_result(shift, self.s12, ep)
+
+    @torch.no_grad()
+    def _rollout_host_kernel(self) -> Dict:
+        """_rollout_host with Params.host_policy = "kernel": _rollout_steps' one act launch per env
+        step in place of the torch ops, then the host env step.  No fp32 staging tensor, no encode
+        copy, no per-step torch moments / normalise / model / RNG ops."""
+        clip = self.p.reward_clip
+        norm, shift = self._rollout_begin()
+        sums = [0.0, 0.0]
+
+        def advance(t, rows, a, k):
             nobs, r, done, info = self.env.step(a)
             # the env's outputs are host tensors: clip / convert there, so each reaches its buffer
             # rows as one upload and the act launch is the step's only kernel
-            if p.reward_clip > 0:
-                r = r.clamp(-p.reward_clip, p.reward_clip)
+            if clip > 0:
+                r = r.clamp(-clip, clip)
             self.rewards[rows].copy_(r.to(torch.float32))
             self.dones[rows].copy_(done.to(torch.float32))
-            ep_ret += float(info["ep_return_sum"])
-            ep_cnt += float(info["ep_count"])
-            obs = nobs.to(torch.float32).to(self.device).contiguous()
-        ep = torch.tensor([ep_ret, ep_cnt], dtype=torch.float64, device=self.device)
-        # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
-        self._launch_act(obs, self.env.t, False, 0, self.key_action, norm, shift, none, none, none,
-                         self.x_buf[T * E:], none, False)
-        self._host_obs = obs
-        self._xT_valid = False
-        self.ext.obs_reduce(self.mom, self.mom.shape[0], O, self.s12, self.epstat, self.ep_sum)
-        return {"count": float(self.N), "s1": self.s12[0], "s2": self.s12[1], "shift": shift,
-                "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
+            sums[0] += float(info["ep_return_sum"])
+            sums[1] += float(info["ep_count"])
+            return nobs.to(torch.float32).to(self.device).contiguous()
+        self._host_obs, ro = self._rollout_steps(self._host_obs.to(self.device, torch.float32).contiguous(), norm,
+                                                 shift, advance, sums)
+        return ro
 
     @torch.no_grad()
     def rollout_stepped(self) -> Dict:
@@ -956,9 +984,7 @@ class HipEngine:
         kinds 0 / 1 and the fused cart-pole (the tests hold it against the fused kernel there).  Per step,
         all on the current stream and with no host sync:
 
-          1. one csrc/act.hip launch: normalise ``obs``, policy MLP, keyed sample -> the step's
-             ``actions`` / ``logp`` / ``x_buf`` rows and the moments in ``self.mom`` (step key
-             ``env.t``, ``e_base`` 0, the engine's action key: the fused kernel's keys)
+          1. _rollout_steps' act launch (after the step-mode observe)
           2. ``env._dynamics`` and ``env._reset_state``: the env's torch ops
           3. one csrc/envstep.hip launch (``env_advance``): VecEnv.step's episode bookkeeping,
              straight into the ``rewards`` / ``dones`` rows, ``env.state`` / ``ep_len`` / ``ep_ret``
@@ -966,11 +992,10 @@ class HipEngine:
              checkpoints them as ever) and ``self.epstat``
           4. ``env.t += 1``, ``obs = env.observe()``
 
-        then a rows-only act launch for the bootstrap rows and one obs_reduce.  The update runs on
-        the usual kernels; the return dict is the other paths'.  With ``bootstrap_time_limit`` step 3
-        is preceded by ``observe()`` of the new state and a rows-only act launch into scratch rows,
-        and ``env_advance_fin`` also writes the step's ``trunc`` row and copies the truncated envs'
-        scratch rows into the slot ``x_fin[t // limit]``; still no host sync."""
+        The update runs on the usual kernels; the return dict is the other paths'.  With
+        ``bootstrap_time_limit`` step 3 is preceded by ``observe()`` of the new state and a rows-only
+        act launch into scratch rows, and ``env_advance_fin`` also writes the step's ``trunc`` row and
+        copies the truncated envs' scratch rows into the slot ``x_fin[t // limit]``; still no host sync."""
         if self.host_env:
             raise RuntimeError("rollout_stepped() steps a builtin tensor env on the device; a host-stepped (gym) env "
                                "takes rollout()")
@@ -978,29 +1003,12 @@ class HipEngine:
             raise ValueError("bootstrap_time_limit is not built for obs_norm_update=step")
         self._flush_value()        # (fp8: the refresh reads every layer; and the reduce rewrites ep_sum)
         self.refresh_fwd_image()
-        p, T, E, O, env = self.p, self.T, self.E, self.O, self.env
-        norm = self.stats
-        if p.obs_norm_update == "step":
-            # as _rollout_host_kernel: every step's batch is merged into the worker-local stats
-            # (csrc/obs.hip, three launches) before the act launch normalises it
-            shift = self.stats.shift().clone()
-            norm = self.local_stats = RunningObsStats(O, self.device)
-            norm.copy_from(self.stats)
-        else:
-            shift = self.stats.shift()   # the fp32 mean itself, as the fused path (no snapshot copy)
-        none = self.no_q
-        clip = float(p.reward_clip)
+        E, env, none, clip = self.E, self.env, self.no_q, float(self.p.reward_clip)
+        norm, shift = self._rollout_begin(snapshot=False)
         if not env.state.is_contiguous():
             env.state = env.state.contiguous()
-        obs = env.observe().to(torch.float32).contiguous()
-        for t in range(T):
-            if p.obs_norm_update == "step":
-                self._observe_step(norm, obs, shift)
-            rows = slice(t * E, (t + 1) * E)
-            a = self.actions[rows]
-            k = env.t & rng.MASK32
-            self._launch_act(obs, k, False, 0, self.key_action, norm, shift, a, self.logp[rows], none,
-                             self.x_buf[rows], self.mom, t == 0)
+
+        def advance(t, rows, a, k):
             new_state, reward, terminal = env._dynamics(a, k)
             reset_state = env._reset_state(k)
             # (.to / .contiguous: no-ops for an env that returns fp32 / bool contiguous tensors)
@@ -1023,14 +1031,8 @@ class HipEngine:
             else:
                 self.ext.env_advance(*adv_args)
             env.t += 1
-            obs = env.observe().to(torch.float32).contiguous()
-        # bootstrap rows [T*E, (T+1)*E): rows only, no MLP, no moments
-        self._launch_act(obs, env.t, False, 0, self.key_action, norm, shift, none, none, none, self.x_buf[T * E:],
-                         none, False)
-        self._xT_valid = False
-        self.ext.obs_reduce(self.mom, self.mom.shape[0], O, self.s12, self.epstat, self.ep_sum)
-        return {"count": float(self.N), "s1": self.s12[0], "s2": self.s12[1], "shift": shift,
-                "ep_return_sum": self.ep_sum[0], "ep_count": self.ep_sum[1], "ep2": self.ep_sum}
+            return env.observe().to(torch.float32).contiguous()
+        return self._rollout_steps(env.observe().to(torch.float32).contiguous(), norm, shift, advance)[1]
 
     @torch.no_grad()
     def _evaluate_stepped(self, E: int, deterministic: bool):
@@ -1105,8 +1107,6 @@ class HipEngine:
                     self.ext.obs_reduce(self.mom, self.mom.shape[0], self.O, self.s12, self.epstat, self.ep_sum)
             else:
                 self.ext.obs_reduce(self.mom, self.mom.shape[0], self.O, self.s12, self.epstat, self.ep_sum)
-            s1, s2 = self.s12[0], self.s12[1]
-            ep = self.ep_sum
         else:
             # per-step obs-norm mode (the reference's filter updates with every observation before
             # normalising it, model.py:68 / train.py:84): step t's normalisation needs the stats of
@@ -1117,15 +1117,12 @@ class HipEngine:
             # + a one-step rollout launch, the steps' moments / episode stats in per-step slices
             # and ONE reduce after the loop.  No host sync either way.
             self._flush_value()
-            shift = self.stats.shift().clone()
-            ls = self.local_stats = RunningObsStats(self.O, self.device)
-            ls.copy_from(self.stats)
+            ls, shift = self._rollout_begin()
             if self._stepnorm_fits():
                 self._launch_stepnorm(ls, shift)
                 self.env.t += self.T
                 self.ext.obs_reduce(self.mom, self.mom.shape[0], self.O, self.s12, self.epstat, self.ep_sum)
-                return {"count": float(self.N), "s1": self.s12[0], "s2": self.s12[1], "shift": shift,
-                        "ep_return_sum": self.ep_sum[0], "ep_count": self.ep_sum[1], "ep2": self.ep_sum}
+                return self._rollout_result(shift, self.s12, self.ep_sum)
             T, nroll = self.T, self.mom.shape[0]
             if self._step_bufs is None or self._step_bufs[0].shape[0] != T:
                 f32 = dict(dtype=torch.float32, device=self.device)
@@ -1136,11 +1133,8 @@ class HipEngine:
                 self._launch_rollout(1, t, self.env.t, ls, shift, mom=mom_t[t], epstat=ep_t[t])
                 self.env.t += 1
             self.ext.obs_reduce(mom_t, T * nroll, self.O, self.s12, ep_t, self.ep_sum)
-            s1, s2 = self.s12[0], self.s12[1]
-            ep = self.ep_sum
         # everything stays on the device: no host sync inside the iteration
-        return {"count": float(self.N), "s1": s1, "s2": s2, "shift": shift,
-                "ep_return_sum": ep[0], "ep_count": ep[1], "ep2": ep}
+        return self._rollout_result(shift, self.s12, self.ep_sum)
 
     @torch.no_grad()
     def evaluate(self, num_envs: int, deterministic: bool = False):
@@ -1175,8 +1169,7 @@ class HipEngine:
         e = self.env
         k = eval_keys(self.p.seed)
         limit = int(min(e.spec.time_limit, self.p.max_episode_length))
-        ints = [self._kind(), E, self.O, self.A, e.state_dim, limit, 1 if self.p.std_convention == "var" else 0,
-                1 if deterministic else 0]
+        ints = [self._kind(), E, self.O, self.A, e.state_dim, limit, self.std_var, 1 if deterministic else 0]
         keys = [k["key_env"], k["key_term"], k["key_reset"], k["key_action"]]
         self.ext.eval_rollout(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data,
                               self.stats.mean_f32, self.stats.inv_std_f32, ret, length, ints, keys, self.qscale)
@@ -1186,8 +1179,7 @@ class HipEngine:
                     norm: RunningObsStats, shift: torch.Tensor, actions: torch.Tensor, logp: torch.Tensor,
                     mu: torch.Tensor, x_out: torch.Tensor, mom: torch.Tensor, mom_init: bool) -> None:
         """one csrc/act.hip launch on the current stream (an empty tensor skips that output)"""
-        ints = [obs.shape[0], self.O, self.A, 1 if self.p.std_convention == "var" else 0, 1 if deterministic else 0,
-                1 if mom_init else 0]
+        ints = [obs.shape[0], self.O, self.A, self.std_var, 1 if deterministic else 0, 1 if mom_init else 0]
         keys = [key_action & 0xFFFFFFFF, e_base & 0xFFFFFFFF, step_key & 0xFFFFFFFF]
         self.ext.policy_act(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data, norm.mean_f32,
                             norm.inv_std_f32, shift, obs, actions, logp, mu, x_out, mom, ints, keys, self.qscale)
@@ -1229,17 +1221,21 @@ class HipEngine:
         return action, logp, mu
 
     @torch.no_grad()
-    def values(self) -> None:
-        self._flush_value()          # the value head must hold its last step
-        M = (self.T + 1) * self.E
-        if self.fp8 and self.heads:
+    def _value_forward(self, x: torch.Tensor, M: int, out: torch.Tensor, head_f8: bool = True) -> None:
+        """V of the first M rows of ``x`` (buffer storage precision) into ``out``: one csrc/mlp.hip launch"""
+        if head_f8 and self.fp8 and self.heads:
             # fp8 mode on the per-head path: the value head's streaming forward with the e4m3 fc1
             # (fc2 / fc3 on the bf16 image; csrc/mlp_head.hip F8)
-            self.ext.mlp_value(self.dt, self.x_buf, self.empty, 0, M, self.wimg, self.layout, self.scales,
-                               self.model.flat.data, self.A, self.values_buf, False, self.qscale, self.wimg_fwd)
+            dt, wimg, w8 = self.dt, self.wimg, self.wimg_fwd
         else:
-            self.ext.mlp_value(self.dt_fwd, self.x_buf, self.empty, 0, M, self.wimg_fwd, self.layout, self.scales,
-                               self.model.flat.data, self.A, self.values_buf, False, self.qscale, self.no_u8)
+            dt, wimg, w8 = self.dt_fwd, self.wimg_fwd, self.no_u8
+        self.ext.mlp_value(dt, x, self.empty, 0, M, wimg, self.layout, self.scales, self.model.flat.data, self.A,
+                           out, False, self.qscale, w8)
+
+    @torch.no_grad()
+    def values(self) -> None:
+        self._flush_value()          # the value head must hold its last step
+        self._value_forward(self.x_buf, (self.T + 1) * self.E, self.values_buf)
         if self.p.compat:
             # Q8 (train.py:109-112, ppo.py:119-122): the reference bootstraps R = V(s_T) from the
             # RAW, un-normalised last state.  Rows [T*E, (T+1)*E) of values_buf get V of the env's
@@ -1251,19 +1247,12 @@ class HipEngine:
             if self.x_raw is None:
                 self.x_raw = torch.empty(self.E, self.d0, dtype=self.sdtype, device=self.device)
             self.x_raw.copy_(self.encode(xr))
-            self.ext.mlp_value(self.dt_fwd, self.x_raw, self.empty, 0, self.E, self.wimg_fwd, self.layout,
-                               self.scales, self.model.flat.data, self.A, self.values_buf[self.N:], False,
-                               self.qscale, self.no_u8)
+            # (the raw rows take the forward image on every layer, in fp8 mode on the per-head path too)
+            self._value_forward(self.x_raw, self.E, self.values_buf[self.N:], head_f8=False)
         if self.boot:
             # V of the final rows: the same forward over x_fin's K * E rows (rows never written are
             # zero rows: a finite value that gae() masks)
-            Mf = self.fin_K * self.E
-            if self.fp8 and self.heads:
-                self.ext.mlp_value(self.dt, self.x_fin, self.empty, 0, Mf, self.wimg, self.layout, self.scales,
-                                   self.model.flat.data, self.A, self.v_fin, False, self.qscale, self.wimg_fwd)
-            else:
-                self.ext.mlp_value(self.dt_fwd, self.x_fin, self.empty, 0, Mf, self.wimg_fwd, self.layout, self.scales,
-                                   self.model.flat.data, self.A, self.v_fin, False, self.qscale, self.no_u8)
+            self._value_forward(self.x_fin, self.fin_K * self.E, self.v_fin)
 
     @torch.no_grad()
     def gae(self) -> None:
