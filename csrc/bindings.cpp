@@ -69,6 +69,11 @@ void check(CT t, const char* name, at::ScalarType st, int64_t min_numel) {
   TORCH_CHECK(t.numel() >= min_numel, name, " has ", t.numel(), " elements, kernel needs >= ", min_numel);
 }
 
+float* fptr(CT t, const char* name, int64_t min_numel) {   // a checked fp32 device array
+  check(t, name, at::kFloat, min_numel);
+  return t.data_ptr<float>();
+}
+
 const float* opt_scales(const torch::Tensor& q) {
   if (!q.defined() || q.numel() == 0) return nullptr;
   check(q, "qscale", at::kFloat, 6);
@@ -445,21 +450,19 @@ int64_t rollout_stepnorm_cap_b(int64_t dt, int64_t rows, std::vector<int64_t> la
   return (int64_t)::rollout_stepnorm_cap((int)dt, a, (int)rows);
 }
 
-// idx_limit: exclusive upper bound every gathered row index must respect (rows of x_buf and of
-// every per-row array).  check_idx=true range-checks the index VALUES on the device (one
-// device->host read).  check_idx=false is only for callers that range-checked the indices on
-// the host before uploading them (the hipGraph-captured update path, which cannot sync).
-int64_t train_lds_bytes_impl(int dt, const Layout& L, int64_t A) {
+// The blank MlpArgs of a shape query: the layout's dims and the action width
+MlpArgs shape_args(const Layout& L, int64_t A) {
   MlpArgs a{};
   for (int i = 0; i < 6; ++i) { a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i]; a.n_out[i] = L.n_out[i]; }
   a.A = (int)A;
-  return (int64_t)mlp_train_lds_bytes(dt, a);
+  return a;
 }
 
-MlpArgs base_mlp(int dt, const Layout& L, const std::vector<double>& scales, torch::Tensor x_buf,
-                 torch::Tensor idx, int64_t row0, int64_t M, torch::Tensor wimg, torch::Tensor flat, int64_t A,
-                 bool check_idx, int64_t idx_limit) {
-  MlpArgs a{};
+// idx_limit: exclusive upper bound of the rows of an idx-less call (rows of x_buf and of every per-row array).  The
+// index VALUES of a gathered call are range-checked by the caller on the host (HipEngine._minibatch): no sync here.
+MlpArgs base_mlp(int dt, const Layout& L, const std::vector<double>& scales, CT x_buf, CT idx, int64_t row0, int64_t M,
+                 CT wimg, CT flat, int64_t A, int64_t idx_limit) {
+  MlpArgs a = shape_args(L, A);
   check(wimg, "wimg", storage_type(dt), wimg_extent(L));
   check(flat, "flat", at::kFloat, A);
   TORCH_CHECK(M > 0, "M must be > 0");
@@ -467,37 +470,25 @@ MlpArgs base_mlp(int dt, const Layout& L, const std::vector<double>& scales, tor
   const int64_t nrows_x = x_buf.numel() / L.d_in[0];
   check(x_buf, "x_buf", storage_type(dt == 2 ? 1 : dt), 1);  // fp8 kernels read a bf16 buffer
   TORCH_CHECK(x_buf.numel() % L.d_in[0] == 0, "x_buf rows must have d_in[0] elements");
-  const int64_t limit = std::min<int64_t>(idx_limit, nrows_x);
   if (idx.defined() && idx.numel() > 0) {
     check(idx, "idx", at::kInt, M);
-    if (check_idx) {
-      auto mm = torch::aminmax(idx.narrow(0, 0, M));
-      const int mn = std::get<0>(mm).item<int>();
-      const int mx = std::get<1>(mm).item<int>();
-      TORCH_CHECK(mn >= 0 && mx < limit, "idx values out of range [0, ", limit, "): min ", mn, " max ", mx);
-    }
     a.idx = idx.data_ptr<int>();
   } else {
-    a.idx = nullptr;
-    TORCH_CHECK(row0 >= 0 && row0 + M <= limit, "row range out of x_buf / per-row arrays");
+    TORCH_CHECK(row0 >= 0 && row0 + M <= std::min<int64_t>(idx_limit, nrows_x), "row range out of x_buf / per-row arrays");
   }
   a.x_buf = x_buf.data_ptr();
   a.x_bytes = (int64_t)x_buf.numel() * (int64_t)x_buf.element_size();
   a.row0 = (int)row0;
   a.M = (int)M;
   a.W = wimg.data_ptr();
-  for (int i = 0; i < 6; ++i) {
-    a.off_w[i] = L.off_w[i]; a.off_wt[i] = L.off_wt[i]; a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i];
-    a.n_out[i] = L.n_out[i]; a.scale[i] = (float)scales.at(i);
-  }
-  a.A = (int)A;
+  for (int i = 0; i < 6; ++i) { a.off_w[i] = L.off_w[i]; a.off_wt[i] = L.off_wt[i]; a.scale[i] = (float)scales.at(i); }
   a.log_std = flat.data_ptr<float>();
   a.x_stream = g_x_stream;
   return a;
 }
 
 // w8 (optional, fp8 mode with dt bf16): the e4m3 image the value head's fc1 reads with qscale
-void set_w8(MlpArgs& a, torch::Tensor w8, torch::Tensor qscale, const Layout& L) {
+void set_w8(MlpArgs& a, CT w8, CT qscale, const Layout& L) {
   if (w8.defined() && w8.numel() > 0) {
     check(w8, "w8", at::kByte, wimg_extent(L));
     check(qscale, "qscale", at::kFloat, 6);
@@ -506,14 +497,11 @@ void set_w8(MlpArgs& a, torch::Tensor w8, torch::Tensor qscale, const Layout& L)
   }
 }
 
-void mlp_value(int64_t dt, torch::Tensor x_buf, torch::Tensor idx, int64_t row0, int64_t M, torch::Tensor wimg,
-               std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat, int64_t A,
-               torch::Tensor v_out, bool check_idx, torch::Tensor qscale, torch::Tensor w8) {
-  Layout L = parse_layout(layout);
-  MlpArgs a = base_mlp((int)dt, L, scales, x_buf, idx, row0, M, wimg, flat, A, check_idx,
-                       std::numeric_limits<int64_t>::max());
-  check(v_out, "v_out", at::kFloat, M);
-  a.v_out = v_out.data_ptr<float>();
+void mlp_value(int64_t dt, CT x_buf, CT idx, int64_t row0, int64_t M, CT wimg, Ints layout,
+               const std::vector<double>& scales, CT flat, int64_t A, CT v_out, CT qscale, CT w8) {
+  const Layout L = parse_layout(layout);
+  MlpArgs a = base_mlp((int)dt, L, scales, x_buf, idx, row0, M, wimg, flat, A, std::numeric_limits<int64_t>::max());
+  a.v_out = fptr(v_out, "v_out", M);
   a.qscale = opt_scales(qscale);
   TORCH_CHECK(!(w8.defined() && w8.numel() > 0) || dt == 1, "w8: the fp8 mode's bf16 value forward only");
   set_w8(a, w8, qscale, L);
@@ -521,165 +509,169 @@ void mlp_value(int64_t dt, torch::Tensor x_buf, torch::Tensor idx, int64_t row0,
   after_launch(__func__);
 }
 
-void mlp_train(int64_t dt, torch::Tensor x_buf, torch::Tensor idx, int64_t row0, int64_t M, torch::Tensor wimg,
-               std::vector<int64_t> layout, std::vector<double> scales, torch::Tensor flat, torch::Tensor log_std_old,
-               int64_t A, torch::Tensor actions, torch::Tensor logp_old, torch::Tensor adv, torch::Tensor ret,
-               torch::Tensor v_old, torch::Tensor mu_prev, torch::Tensor v_prev, std::vector<int64_t> opts,
-               std::vector<double> fopts, std::vector<torch::Tensor> tbufs, int64_t ldT, torch::Tensor part,
-               bool check_idx, bool xT_ready, torch::Tensor w8, torch::Tensor qscale, torch::Tensor q8_amax,
-               int64_t q8_step) {
+// fp8 mode's gradient-amax ring (csrc/common.h Q8), checked: the slots of step `step` (-1: the calibration pass) —
+// its |g| maxima go to acc, its scales come from rd (the step before's maxima), clr is zeroed for the step after
+struct Q8Ring { unsigned *acc, *rd, *clr; };
+Q8Ring q8_ring(CT q8_amax, int64_t step) {
+  check(q8_amax, "q8_amax", at::kInt, 3 * Q8_SLOT);
+  unsigned* base = reinterpret_cast<unsigned*>(q8_amax.data_ptr<int>());
+  const int64_t e = ((step % 3) + 3) % 3;
+  return {base + Q8_SLOT * e, base + Q8_SLOT * ((e + 2) % 3), base + Q8_SLOT * ((e + 1) % 3)};
+}
+
+int64_t train_lds_bytes(int64_t dt, std::vector<int64_t> layout, int64_t A) {
+  return (int64_t)mlp_train_lds_bytes((int)dt, shape_args(parse_layout(layout), A));
+}
+
+// MlpArgs of one update launch, checked: what the tile kernel, the per-head kernels and the 32x32 policy head
+// share.  A binding passes its kernel's row tile ROWS, workgroup waves nw (the timestamp hook's extent), the
+// operand buffers' storage type and the parsed layout; the rest of this list leads its own.  tbufs: xT h1pT h2pT
+// h1vT h2vT g1pT g2pT g3pT g1vT g2vT g3vT, rows of ldT elements; idx empty: rows row0 .. row0 + M of x_buf; loss:
+// loss_kind (0 ppo, 1 dppo_ref), value_loss (0 mse, 1 clipped_half), std_var, first_step, clip, ent_coeff; part:
+// [ceil(M / ROWS)][npart] per-workgroup partial rows; xT_ready: xT holds the rows already.
+using Tensors = const std::vector<torch::Tensor>&;
+MlpArgs train_args(int ROWS, int64_t nw, at::ScalarType operand, const Layout& L, int64_t dt, int64_t A, Tensors tbufs,
+                   CT x_buf, CT idx, int64_t row0, int64_t M, CT wimg, const std::vector<double>& scales, CT flat,
+                   CT log_std_old, CT actions, CT logp_old, CT adv, CT ret, CT v_old, CT mu_prev, CT v_prev,
+                   const std::vector<double>& loss, int64_t ldT, CT part, int64_t npart, bool xT_ready) {
   TORCH_CHECK(dt != 2, "the fp8 mode's update runs in bf16 (its e4m3 parts: the value fc1 image w8 and the wgrad operands q8_amax)");
-  Layout L = parse_layout(layout);
   TORCH_CHECK(A > 0, "A");
   check(actions, "actions", at::kFloat, A);
   const int64_t nrows = actions.numel() / A;
-  MlpArgs a = base_mlp((int)dt, L, scales, x_buf, idx, row0, M, wimg, flat, A, check_idx, nrows);
-  TORCH_CHECK(opts.size() == 5 || opts.size() == 7 || opts.size() == 8,
-              "opts: loss_kind, value_loss, std_var, first_step, npart[, head, part_dw[, t32]]");
-  // head >= 0: one head's per-head streaming kernel (csrc/mlp_head.hip; 0 policy, 1 value) with
-  // its fused narrow-layer weight gradient at partial column part_dw (policy [32][128], value [128])
-  const int head = opts.size() >= 7 ? (int)opts[5] : -1;
-  const int part_dw = opts.size() >= 7 ? (int)opts[6] : 0;
-  // t32: the policy head's transposed-chain 32x32 kernel (csrc/phead.hip): h1p / g1p / g2p and,
-  // unless xT_ready, the observation rows into xT, ROW-MAJOR (the engine's wgrad reads them so: its
-  // rm flags).  opts[7] == 1 also sums p_fc2's weight gradient in the kernel (no h1p / g2p), 2
-  // stores h1p / g2p.  (The value head's update stays on the 16x16 kernel: docs/ARCHITECTURE.md §13.)
-  const bool t32 = opts.size() == 8 && opts[7] != 0;
-  const bool p2 = t32 && opts[7] == 1;
-  TORCH_CHECK(head >= -1 && head <= 1, "head: -1 (both heads, one kernel), 0 policy, 1 value");
-  TORCH_CHECK(fopts.size() == 2, "fopts: clip, ent_coeff");
+  MlpArgs a = base_mlp((int)dt, L, scales, x_buf, idx, row0, M, wimg, flat, A, nrows);
+  TORCH_CHECK(loss.size() == 6, "loss: loss_kind, value_loss, std_var, first_step, clip, ent_coeff");
   TORCH_CHECK(tbufs.size() == 11, "11 transposed buffers");
-  check(logp_old, "logp_old", at::kFloat, nrows);
-  check(adv, "adv", at::kFloat, nrows);
-  check(ret, "ret", at::kFloat, nrows);
-  check(v_old, "v_old", at::kFloat, nrows);
-  check(mu_prev, "mu_prev", at::kFloat, nrows * A);
-  check(v_prev, "v_prev", at::kFloat, nrows);
-  check(log_std_old, "log_std_old", at::kFloat, A);
-  if (head >= 0)
-    TORCH_CHECK((dt == 3 || dt == 1) && mlp_head_applies(a), "the per-head kernels cover split-bf16 / bf16 and the reference network only");
-  const int ROWS = head >= 0 ? mlp_head_rows() : mlp_train_rows((int)dt, a);
-  TORCH_CHECK(head >= 0 || train_lds_bytes_impl((int)dt, L, A) <= 160 * 1024, "mlp_train tile does not fit LDS");
+  a.actions = actions.data_ptr<float>();
+  a.logp_old = fptr(logp_old, "logp_old", nrows);
+  a.adv = fptr(adv, "adv", nrows);
+  a.ret = fptr(ret, "ret", nrows);
+  a.v_old = fptr(v_old, "v_old", nrows);
+  a.mu_prev = fptr(mu_prev, "mu_prev", nrows * A);
+  a.v_prev = fptr(v_prev, "v_prev", nrows);
+  a.log_std_old = fptr(log_std_old, "log_std_old", A);
   const int64_t Mpad = ((M + ROWS - 1) / ROWS) * ROWS;
   TORCH_CHECK(ldT >= Mpad && ldT % 32 == 0, "ldT must cover M padded to the row tile and be a multiple of 32");
   // rows each transposed buffer must hold (writer side)
   const int64_t need[11] = {L.d_in[0], L.d_in[1], L.d_in[2], L.d_in[4], L.d_in[5],
                             L.n_out[0], L.n_out[1], L.n_out[2], L.n_out[3], L.n_out[4], L.n_out[5]};
-  // q8_amax (fp8 mode, per-head bf16 update): the 3 x 4 slot ring of gradient maxima; the
-  // operand buffers then hold e4m3 bytes (csrc/common.h Q8)
-  const bool q8 = q8_amax.defined() && q8_amax.numel() > 0;
-  if (q8) {
-    TORCH_CHECK(dt == 1 && head >= 0, "e4m3 wgrad operands: the fp8 mode's per-head bf16 update only");
-    check(q8_amax, "q8_amax", at::kInt, 3 * Q8_SLOT);
-    unsigned* base = reinterpret_cast<unsigned*>(q8_amax.data_ptr<int>());
-    const int64_t e = ((q8_step % 3) + 3) % 3;   // step -1: the calibration pass
-    a.q8_acc = base + Q8_SLOT * e;
-    a.q8_rd = base + Q8_SLOT * ((e + 2) % 3);
-    a.q8_clr = base + Q8_SLOT * ((e + 1) % 3);
-  }
-  for (int i = 0; i < 11; ++i)
-    check(tbufs[i], "transposed buffer", q8 ? at::kByte : storage_type((int)dt), need[i] * ldT);
-  const int npart = (int)opts[4];
-  TORCH_CHECK(npart >= 8 + A || (head == 1 && npart >= 8), "npart too small");
-  if (head == 0) TORCH_CHECK(part_dw >= 8 + A && part_dw + 32 * 128 <= npart, "part_dw: policy dW_mu block");
-  if (head == 1) TORCH_CHECK(part_dw >= 8 && part_dw + 128 <= npart, "part_dw: value dW_v block");
-  a.part_dw = part_dw;
-  const int nblk = (int)(Mpad / ROWS);
-  check(part, "part", at::kFloat, (int64_t)nblk * npart);
-  a.log_std_old = log_std_old.data_ptr<float>();
-  a.actions = actions.data_ptr<float>();
-  a.logp_old = logp_old.data_ptr<float>();
-  a.adv = adv.data_ptr<float>();
-  a.ret = ret.data_ptr<float>();
-  a.v_old = v_old.data_ptr<float>();
-  a.mu_prev = mu_prev.data_ptr<float>();
-  a.v_prev = v_prev.data_ptr<float>();
-  a.loss_kind = (int)opts[0];
-  a.value_loss = (int)opts[1];
-  a.std_var = (int)opts[2];
-  a.first_step = (int)opts[3];
-  a.npart = npart;
-  a.clip = (float)fopts[0];
-  a.ent_coeff = (float)fopts[1];
   void** dst[11] = {&a.xT, &a.h1pT, &a.h2pT, &a.h1vT, &a.h2vT, &a.g1pT, &a.g2pT, &a.g3pT, &a.g1vT, &a.g2vT, &a.g3vT};
-  for (int i = 0; i < 11; ++i) *dst[i] = tbufs[i].data_ptr();
+  for (int i = 0; i < 11; ++i) {
+    check(tbufs[i], "transposed buffer", operand, need[i] * ldT);
+    *dst[i] = tbufs[i].data_ptr();
+  }
   a.ldT = (int)ldT;
-  // a precomputed xT is only valid for the identity row order covering the whole buffer
-  // (t32 policy: x_buf itself is the wgrad's X operand then, so only the row order matters)
-  TORCH_CHECK(!xT_ready || (a.idx == nullptr && row0 == 0 && (ldT == M || (t32 && head == 0))),
-              "xT_ready needs a full-batch call");
+  const int64_t nblk = Mpad / ROWS;
+  a.part = fptr(part, "part", nblk * npart);
+  a.npart = (int)npart;
+  a.loss_kind = (int)loss[0]; a.value_loss = (int)loss[1]; a.std_var = (int)loss[2]; a.first_step = (int)loss[3];
+  a.clip = (float)loss[4]; a.ent_coeff = (float)loss[5];
+  // a precomputed xT is only valid for the identity row order from row 0
+  TORCH_CHECK(!xT_ready || (a.idx == nullptr && row0 == 0), "xT_ready needs a full-batch call");
   a.xT_ready = xT_ready ? 1 : 0;
   if (g_tstamp != nullptr) {
-    // (the 32x32 policy head takes no stamps)
-    const int64_t nw = head >= 0 ? mlp_head_waves(head) : mlp_train_waves((int)dt, a);
     TORCH_CHECK(g_tstamp_numel >= ((nblk + g_tstamp_every - 1) / g_tstamp_every) * nw * 16, "tstamp buffer too small");
     a.tstamp = g_tstamp;
     a.tstamp_every = g_tstamp_every;
   }
-  a.part = part.data_ptr<float>();
-  TORCH_CHECK(!(w8.defined() && w8.numel() > 0) || (dt == 1 && head >= 0), "w8: the fp8 mode's per-head bf16 update only");
-  set_w8(a, w8, qscale, L);
-  if (t32) {   // the row-major operand rows the kernels write are whole padded widths
-    const int64_t pn = !p2 ? 128 : 0;   // h1p / g2p
-    const int64_t wid[11] = {!xT_ready ? L.d_in[0] : 0, pn, 0, 0, 0, 128, pn, 0, 0, 0, 0};
-    for (int i = 0; i < 11; ++i)
-      TORCH_CHECK(tbufs[i].numel() >= wid[i] * ldT, "t32 head: row-major operand buffer ", i, " too small");
+  return a;
+}
+
+// The three update bindings: train_args' parameters (from dt on; the pack P, deduced from it), then each kernel's own
+constexpr const char* HEADS_ONLY = "the per-head kernels cover split-bf16 / bf16 and the reference network only";
+template <class F> struct TrainBind;
+template <class... P>
+struct TrainBind<MlpArgs (*)(int, int64_t, at::ScalarType, const Layout&, int64_t, int64_t, Tensors, P...)> {
+  // The two-head tile kernel (csrc/mlp.hip)
+  static void mlp_train(int64_t dt, int64_t A, Tensors tbufs, Ints layout, P... p) {
+    const Layout L = parse_layout(layout);
+    const MlpArgs s = shape_args(L, A);
+    TORCH_CHECK(mlp_train_lds_bytes((int)dt, s) <= 160 * 1024, "mlp_train tile does not fit LDS");
+    const MlpArgs a = train_args(mlp_train_rows((int)dt, s), mlp_train_waves((int)dt, s), storage_type((int)dt), L, dt,
+                                 A, tbufs, p...);
+    TORCH_CHECK(a.npart >= 8 + A, "npart too small");
+    TORCH_CHECK(!a.xT_ready || a.ldT == a.M, "xT_ready needs a full-batch call");   // (xT: the whole buffer's rows)
+    launch_mlp_train((int)dt, a, cur_stream());
+    after_launch(__func__);
   }
-  if (t32) {
-    TORCH_CHECK(head == 0 && !q8 && a.W8 == nullptr && phead_shape_ok(a), "phead: the policy head at bf16x3 / bf16");
+
+  // One head's streaming kernel (csrc/mlp_head.hip; head 0 policy, 1 value) with its fused narrow-layer weight
+  // gradient at partial column part_dw (policy dW_mu [32][128], value dW_v [128]).  fp8 mode (dt bf16), else empty
+  // tensors: w8 / qscale, the e4m3 image the head's fc1 reads; q8_amax / q8_step, the gradient-amax ring — the
+  // operand buffers then hold e4m3 bytes (csrc/common.h Q8).
+  static void mlp_head_train(int64_t dt, int64_t A, Tensors tbufs, Ints layout, P... p, int64_t head, int64_t part_dw,
+                             CT w8, CT qscale, CT q8_amax, int64_t q8_step) {
+    const Layout L = parse_layout(layout);
+    TORCH_CHECK(head == 0 || head == 1, "head: 0 policy, 1 value");
+    TORCH_CHECK((dt == 3 || dt == 1) && mlp_head_applies(shape_args(L, A)), HEADS_ONLY);
+    TORCH_CHECK(!(w8.defined() && w8.numel() > 0) || dt == 1, "w8: the fp8 mode's per-head bf16 update only");
+    const bool q8 = q8_amax.defined() && q8_amax.numel() > 0;
+    TORCH_CHECK(!q8 || dt == 1, "e4m3 wgrad operands: the fp8 mode's per-head bf16 update only");
+    const Q8Ring ring = q8 ? q8_ring(q8_amax, q8_step) : Q8Ring{};
+    MlpArgs a = train_args(mlp_head_rows(), mlp_head_waves((int)head), q8 ? at::kByte : storage_type((int)dt), L, dt, A,
+                           tbufs, p...);
+    a.q8_acc = ring.acc; a.q8_rd = ring.rd; a.q8_clr = ring.clr;
+    TORCH_CHECK(a.npart >= (head == 1 ? 8 : 8 + A), "npart too small");
+    if (head == 0) TORCH_CHECK(part_dw >= 8 + A && part_dw + 32 * 128 <= a.npart, "part_dw: policy dW_mu block");
+    if (head == 1) TORCH_CHECK(part_dw >= 8 && part_dw + 128 <= a.npart, "part_dw: value dW_v block");
+    a.part_dw = (int)part_dw;
+    TORCH_CHECK(!a.xT_ready || a.ldT == a.M, "xT_ready needs a full-batch call");
+    set_w8(a, w8, qscale, L);
+    launch_mlp_head((int)dt, (int)head, a, cur_stream());
+    after_launch(__func__);
+  }
+
+  // The policy head's transposed-chain 32x32 kernel (csrc/phead.hip): h1p / g1p / g2p and, unless xT_ready, the
+  // observation rows into xT, ROW-MAJOR (the engine's wgrad reads them so: its rm flags; under xT_ready x_buf itself
+  // is the wgrad's X operand, so only the row order matters).  dW_mu is summed at partial column part_dw; p2 also
+  // sums p_fc2's weight gradient behind it (no h1p / g2p stores).  (The value head's update stays on the 16x16
+  // kernel: docs/ARCHITECTURE.md §13.)
+  static void phead_train(int64_t dt, int64_t A, Tensors tbufs, Ints layout, P... p, int64_t part_dw, bool p2) {
+    const Layout L = parse_layout(layout);
+    const MlpArgs s = shape_args(L, A);
+    TORCH_CHECK((dt == 3 || dt == 1) && mlp_head_applies(s), HEADS_ONLY);
+    TORCH_CHECK(phead_shape_ok(s), "phead: the policy head at bf16x3 / bf16");
+    MlpArgs a = train_args(mlp_head_rows(), mlp_head_waves(0), storage_type((int)dt), L, dt, A, tbufs, p...);
+    const int64_t ldT = a.ldT, npart = a.npart;
+    TORCH_CHECK(npart >= 8 + A, "npart too small");
+    TORCH_CHECK(part_dw >= 8 + A && part_dw + 32 * 128 <= npart, "part_dw: policy dW_mu block");
     TORCH_CHECK(part_dw + 32 * 128 + (p2 ? 128 * 128 : 0) <= npart,
                 "phead: the dW_mu (and dW_p2) blocks must fit the partial row");
-    const int64_t eb = dt == 3 ? 4 : 2;
+    a.part_dw = (int)part_dw;
+    // the row-major operand rows the kernel writes are whole padded widths
+    const int64_t pn = !p2 ? 128 : 0;   // h1p / g2p
+    const int64_t wid[11] = {!a.xT_ready ? L.d_in[0] : 0, pn, 0, 0, 0, 128, pn, 0, 0, 0, 0};
+    for (int i = 0; i < 11; ++i)
+      TORCH_CHECK(tbufs[i].numel() >= wid[i] * ldT, "t32 head: row-major operand buffer ", i, " too small");
+    const int64_t eb = dt == 3 ? 4 : 2, nblk = (a.M + mlp_head_rows() - 1) / mlp_head_rows();
     TORCH_CHECK(ldT * std::max<int64_t>(L.d_in[0], 128) * eb < (int64_t(1) << 31), "phead: row-major operands beyond 2 GiB");
-    TORCH_CHECK((int64_t)nblk * npart * 4 < (int64_t(1) << 31), "phead: partial buffer beyond 2 GiB");
-    TORCH_CHECK(ldT % phead_rows() == 0 && Mpad <= ldT && (L.d_in[0] >> 4) / (dt == 3 ? 1 : 2) >= 3,
+    TORCH_CHECK(nblk * npart * 4 < (int64_t(1) << 31), "phead: partial buffer beyond 2 GiB");
+    TORCH_CHECK(ldT % phead_rows() == 0 && (L.d_in[0] >> 4) / (dt == 3 ? 1 : 2) >= 3,
                 "phead: ldT covers whole workgroups; fc1 has >= 3 stages");
     launch_phead_train((int)dt, a, p2 ? 1 : 0, cur_stream());
-  } else if (head >= 0) {
-    launch_mlp_head((int)dt, (int)head, a, cur_stream());
-  } else {
-    launch_mlp_train((int)dt, a, cur_stream());
+    after_launch(__func__);
   }
-  after_launch(__func__);
-}
+};
+using TrainB = TrainBind<decltype(&train_args)>;
 
 // the transposed-chain policy head covers this (dtype, network, action width)
 bool phead_train_applies(int64_t dt, std::vector<int64_t> layout, int64_t A) {
-  const Layout L = parse_layout(layout);
-  MlpArgs a{};
-  for (int i = 0; i < 6; ++i) { a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i]; a.n_out[i] = L.n_out[i]; }
-  a.A = (int)A;
-  return (dt == 3 || dt == 1) && phead_shape_ok(a) != 0 && (L.d_in[0] >> 4) / (dt == 3 ? 1 : 2) >= 3;
+  const MlpArgs a = shape_args(parse_layout(layout), A);
+  return (dt == 3 || dt == 1) && phead_shape_ok(a) != 0 && (a.d_in[0] >> 4) / (dt == 3 ? 1 : 2) >= 3;
 }
 
 // the per-head kernels cover this (dtype, network); x_bytes is irrelevant to them (64-bit rows)
 bool head_applies(int64_t dt, std::vector<int64_t> layout, int64_t A) {
-  const Layout L = parse_layout(layout);
-  MlpArgs a{};
-  for (int i = 0; i < 6; ++i) { a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i]; a.n_out[i] = L.n_out[i]; }
-  a.A = (int)A;
-  return (dt == 3 || dt == 1) && mlp_head_applies(a) != 0;
-}
-
-int64_t train_lds_bytes(int64_t dt, std::vector<int64_t> layout, int64_t A) {
-  return train_lds_bytes_impl((int)dt, parse_layout(layout), A);
+  return (dt == 3 || dt == 1) && mlp_head_applies(shape_args(parse_layout(layout), A)) != 0;
 }
 
 int64_t train_rows(int64_t dt, std::vector<int64_t> layout, int64_t A, int64_t x_bytes) {
-  const Layout L = parse_layout(layout);
-  MlpArgs a{};
-  for (int i = 0; i < 6; ++i) { a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i]; a.n_out[i] = L.n_out[i]; }
-  a.A = (int)A;
+  MlpArgs a = shape_args(parse_layout(layout), A);
   a.x_bytes = x_bytes;
   return mlp_train_rows((int)dt, a);
 }
 
 int64_t train_waves(int64_t dt, std::vector<int64_t> layout, int64_t A) {
-  const Layout L = parse_layout(layout);
-  MlpArgs a{};
-  for (int i = 0; i < 6; ++i) { a.d_in[i] = L.d_in[i]; a.d_out[i] = L.d_out[i]; a.n_out[i] = L.n_out[i]; }
-  a.A = (int)A;
-  return mlp_train_waves((int)dt, a);
+  return mlp_train_waves((int)dt, shape_args(parse_layout(layout), A));
 }
 
 void set_mlp_rows(int64_t rows) {
@@ -689,8 +681,6 @@ void set_mlp_rows(int64_t rows) {
 
 // dt 2 (fp8 mode): e4m3 operands; q8_amax / q8_step name the slot the update read its gradient
 // scales from, q8_t the gradient tensor of each layer (-1: none), q8_xs the activation scales
-F8Shadow f8_shadow(torch::Tensor img, torch::Tensor lid, torch::Tensor qs, int64_t n);
-
 WgradArgs wgrad_args(int64_t dt, std::vector<torch::Tensor> gT, std::vector<torch::Tensor> xT,
                      std::vector<int64_t> g_rows, std::vector<int64_t> x_rows, int64_t ld, torch::Tensor tasks,
                      torch::Tensor tasks_host, torch::Tensor slab, torch::Tensor q8_amax, int64_t q8_step,
@@ -746,10 +736,8 @@ WgradArgs wgrad_args(int64_t dt, std::vector<torch::Tensor> gT, std::vector<torc
   a.slab = slab.data_ptr<float>();
   TORCH_CHECK(dt == 0 || dt == 1 || dt == 2 || dt == 3, "wgrad runs in fp32, bf16, e4m3 or bf16x3");
   if (dt == 2) {
-    check(q8_amax, "q8_amax", at::kInt, 3 * Q8_SLOT);
+    a.q8_rd = q8_ring(q8_amax, q8_step).rd;
     TORCH_CHECK(q8_t.size() == 6 && q8_xs.size() == 6, "q8_t / q8_xs: one per layer");
-    const int64_t e = ((q8_step % 3) + 3) % 3;
-    a.q8_rd = reinterpret_cast<const unsigned*>(q8_amax.data_ptr<int>()) + Q8_SLOT * ((e + 2) % 3);
     for (int i = 0; i < ntasks; ++i) {
       const int l = tp[WGRAD_TASK_INTS * i];
       TORCH_CHECK(q8_t[l] >= 0 && q8_t[l] < 4 && q8_xs[l] > 0, "e4m3 wgrad task on a layer without operand scales");
@@ -1142,7 +1130,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("env_advance_fin", &env_advance_fin);
   m.def("rollout_stepnorm_cap", &rollout_stepnorm_cap_b);
   m.def("mlp_value", &mlp_value);
-  m.def("mlp_train", &mlp_train);
+  m.def("mlp_train", &TrainB::mlp_train);
+  m.def("mlp_head_train", &TrainB::mlp_head_train);
+  m.def("phead_train", &TrainB::phead_train);
   m.def("head_applies", &head_applies);
   m.def("phead_train_applies", &phead_train_applies);
   m.def("set_phead", [](int64_t on) { set_phead((int)on); });

@@ -690,39 +690,25 @@ size_t train_lds_any(const MlpArgs& a) {
 }  // namespace
 
 extern "C" void launch_mlp_train(int dt, const MlpArgs& a, hipStream_t s) {
-  if (dt == DT_F32) train_t<DT_F32>(a, s);
-  else if (dt == DT_BF16) train_t<DT_BF16>(a, s);
-  else if (dt == DT_S3) train_t<DT_S3>(a, s);
-  else train_t<DT_FP8>(a, s);
+  dispatch_dt(dt, [&](auto d) { train_t<decltype(d)::value>(a, s); });
 }
 
 extern "C" void launch_mlp_value(int dt, const MlpArgs& a, hipStream_t s) {
-  if (dt == DT_F32) value_t<DT_F32>(a, s);
-  else if (dt == DT_BF16) value_t<DT_BF16>(a, s);
-  else if (dt == DT_S3) value_t<DT_S3>(a, s);
-  else value_t<DT_FP8>(a, s);
+  dispatch_dt(dt, [&](auto d) { value_t<decltype(d)::value>(a, s); });
 }
 
 extern "C" size_t mlp_train_lds_bytes(int dt, const MlpArgs& a) {
-  if (dt == DT_F32) return train_lds_any<DT_F32>(a);
-  if (dt == DT_BF16) return train_lds_any<DT_BF16>(a);
-  if (dt == DT_S3) return train_lds_any<DT_S3>(a);
-  return train_lds_any<DT_FP8>(a);
+  return dispatch_dt(dt, [&](auto d) { return train_lds_any<decltype(d)::value>(a); });
 }
 
 extern "C" int mlp_train_rows(int dt, const MlpArgs& a) {
-  if (dt == DT_F32) return train_rows_t<DT_F32>(a);
-  if (dt == DT_BF16) return train_rows_t<DT_BF16>(a);
-  if (dt == DT_S3) return train_rows_t<DT_S3>(a);
-  return train_rows_t<DT_FP8>(a);
+  return dispatch_dt(dt, [&](auto d) { return train_rows_t<decltype(d)::value>(a); });
 }
 
 extern "C" void set_mlp_rows_override(int rows) { g_rows_override = rows; }
 extern "C" void set_s3_train_waves(int nw) { g_s3_train_waves = nw == 8 ? 8 : 4; }
 extern "C" void set_s3_value_waves(int nw) { g_s3_value_waves = nw == 8 ? 8 : 4; }
+// (fp32: the 16-row tile, so 4)
 extern "C" int mlp_train_waves(int dt, const MlpArgs& a) {
-  if (dt == DT_F32) return 4;
-  if (dt == DT_BF16) return train_waves_t<DT_BF16>(a);
-  if (dt == DT_S3) return train_waves_t<DT_S3>(a);
-  return train_waves_t<DT_FP8>(a);
+  return dispatch_dt(dt, [&](auto d) { return train_waves_t<decltype(d)::value>(a); });
 }

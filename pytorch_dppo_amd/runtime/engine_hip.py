@@ -334,6 +334,8 @@ class HipEngine:
         self.pending_steps = 0       # value steps left pending on a process-group all-reduce
         # world-size-1 fast path: grad_gather + no-clip Adam in one launch (fused_apply=False: off)
         self.fused_apply = bool(params.fused_apply)
+        mgn = params.max_grad_norm
+        self.max_norm = float(mgn) if (mgn is not None and mgn > 0) else 0.0    # the global-norm clip (0.0: off)
         self.idx_dev = torch.zeros(self.ldT, dtype=torch.int32, **dev)
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.std_var = 1 if params.std_convention == "var" else 0   # the policy launches' log_std flag
@@ -1230,7 +1232,7 @@ class HipEngine:
         else:
             dt, wimg, w8 = self.dt_fwd, self.wimg_fwd, self.no_u8
         self.ext.mlp_value(dt, x, self.empty, 0, M, wimg, self.layout, self.scales, self.model.flat.data, self.A,
-                           out, False, self.qscale, w8)
+                           out, self.qscale, w8)
 
     @torch.no_grad()
     def values(self) -> None:
@@ -1280,9 +1282,14 @@ class HipEngine:
             m, s = self.adv.mean(), self.adv.std()
             self.adv.sub_(m).div_(s + 1e-8)
 
-    def begin_update(self) -> None:
-        if self.p.loss == "dppo_ref":   # only the reference loss reads the previous log_std
+    def _keep_log_std(self) -> None:
+        """train.py:164: log_std as this step's kernels read it, kept for the next step before Adam moves it (only the
+        reference loss reads it)"""
+        if self.p.loss == "dppo_ref":
             self.log_std_old.copy_(self.model.flat.data[:self.A])
+
+    def begin_update(self) -> None:
+        self._keep_log_std()
         self._first_step = True
         if self.gate is not None:
             self.gate.zero_()
@@ -1330,9 +1337,7 @@ class HipEngine:
         """the one-kernel path's grad(idx, apply=True): one gradient range, no clipping (the Adam
         step needs no global norm first), eager launches (the host knows the step number), and
         no all-reduce between the gradient and the update (the caller checks: world size 1)."""
-        p = self.p
-        clip = p.max_grad_norm is not None and p.max_grad_norm > 0
-        return (self.fused_apply and not extra_grad and not clip
+        return (self.fused_apply and not extra_grad and not self.max_norm
                 and (self.heads or (len(self.buckets) == 1 and self.buckets[0]["partials"])))
 
     def step(self, idx: Optional[torch.Tensor], extra_grad: float = 0.0, allreduce=None,
@@ -1359,7 +1364,6 @@ class HipEngine:
         Clipping (a global norm over both heads), the Q1 extra gradient and the one-kernel tile
         update take the whole-vector path."""
         p = self.p
-        clip = p.max_grad_norm is not None and p.max_grad_norm > 0
         if self.gate is not None:
             self._gated_step(idx, extra_grad, allreduce, mean)
             return
@@ -1374,7 +1378,7 @@ class HipEngine:
             else:
                 self._flush_value()
                 self.grad(idx)
-            if (self.heads and getattr(allreduce, "side", False) and not clip and not extra_grad
+            if (self.heads and getattr(allreduce, "side", False) and not self.max_norm and not extra_grad
                     and (p.overlap_value_epochs or (last and p.overlap_rollout))):
                 self._split_step_side(allreduce)
                 return
@@ -1382,16 +1386,10 @@ class HipEngine:
             allreduce(self.grad_flat)           # sum / mean in stream order: no host-side scaling
             self.apply(extra_grad)
             return
-        if not self.heads:
-            self.grad(idx)
-            if allreduce is not None:
-                self._reduce_wait(allreduce(self.grad_flat), self.grad_flat, mean)
-            self.apply(extra_grad)
-            return
         mbt = self._minibatch(idx)
-        if clip or extra_grad:
-            self._flush_value()
-            self._heads_grad(*mbt)
+        if not self.heads or self.max_norm or extra_grad:   # the whole-vector path
+            self._flush_value()                 # (only the per-head chains leave a value step pending)
+            self._grad_chain(*mbt)
             if allreduce is not None:
                 self._reduce_wait(allreduce(self.grad_flat), self.grad_flat, mean)
             self.apply(extra_grad)
@@ -1487,38 +1485,47 @@ class HipEngine:
         if mean:
             t.mul_(1.0 / torch.distributed.get_world_size())
 
-    def _heads_grad(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
-        for h in (0, 1):
-            self._head_chain(h, idx_t, first, xt_ready, xmode)
+    def _grad_chain(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
+        """the minibatch gradient into grad_flat: both per-head chains, or the tile kernel's one"""
+        if self.heads:
+            for h in (0, 1):
+                self._head_chain(h, idx_t, first, xt_ready, xmode)
+        else:
+            self._launch_grad(idx_t, first, xt_ready)
+
+    def _update_args(self, idx_t, first: bool, xt_ready: bool, part: torch.Tensor) -> tuple:
+        """the positional block that leads ext.mlp_train, ext.mlp_head_train and ext.phead_train (csrc/bindings.cpp
+        train_args): dt, A, the 11 operand buffers, the layout; x_buf, idx, row0, M; the weight image, scales, flat,
+        log_std_old; actions, logp, adv, ret, values and mu_prev / v_prev; loss = [loss_kind, value_loss, std_var,
+        first_step, clip, ent_coeff]; ldT; the partial rows and their width; xt_ready"""
+        p = self.p
+        loss = [float(p.loss != "ppo"), float(p.value_loss != "mse"), float(self.std_var), float(first),
+                float(p.clip), float(p.ent_coeff)]
+        return (self.dt, self.A, self.tbufs, self.layout, self.x_buf, idx_t, 0, self.mb, self.wimg, self.scales,
+                self.model.flat.data, self.log_std_old, self.actions, self.logp, self.adv, self.ret, self.values_buf,
+                self.mu_prev, self.v_prev, loss, self.ldT, part, part.shape[1], xt_ready)
 
     def _head_kernel(self, h: int, idx_t, first: bool, xt_ready: bool, part: torch.Tensor, part_dw: int) -> None:
-        p, M = self.p, self.mb
-        t32 = h == 0 and self.phead
-        opts = [0 if p.loss == "ppo" else 1, 0 if p.value_loss == "mse" else 1,
-                1 if p.std_convention == "var" else 0, 1 if first else 0, part.shape[1], h, part_dw,
-                (1 if self.phead_p2 else 2) if t32 else 0]
-        # (the 32x32 policy kernel: xt_ready as _minibatch resolved it — it writes X rows into xT
-        # only for x-mode "mb", a minibatch)
-        # fp8: the value head's fc1 on the e4m3 image; the policy's GEMMs only with fp8_policy_gemms
-        w8 = self._w8() if (h == 1 or p.fp8_policy_gemms) else (self.no_u8, self.no_q)
-
-        def launch(q8_step):
-            self.ext.mlp_train(self.dt, self.x_buf, idx_t, 0, M, self.wimg, self.layout, self.scales,
-                               self.model.flat.data, self.log_std_old, self.A, self.actions, self.logp, self.adv,
-                               self.ret, self.values_buf, self.mu_prev, self.v_prev, opts,
-                               [float(p.clip), float(p.ent_coeff)], self.tbufs, self.ldT, part, False, xt_ready,
-                               *w8, self.q8_amax if self.q8 else self.empty, q8_step)
-        if self.q8 and not self._q8_cal[h]:
-            # the first step of this engine: one pass as step -1 only to record the gradient maxima
-            # the step-0 scales come from (its stores and partials are overwritten by the real one;
-            # the reference loss's mu_prev / v_prev writes are idempotent)
-            launch(-1)
-            self._q8_cal[h] = True
-        launch(self._q8_step)
+        args = self._update_args(idx_t, first, xt_ready, part)
+        if h == 0 and self.phead:
+            # (the 32x32 policy kernel: xt_ready as _minibatch resolved it — it writes X rows into xT
+            # only for x-mode "mb", a minibatch)
+            self.ext.phead_train(*args, part_dw, self.phead_p2)
+        else:
+            # fp8: the value head's fc1 on the e4m3 image; the policy's GEMMs only with fp8_policy_gemms
+            w8 = self._w8() if (h == 1 or self.p.fp8_policy_gemms) else (self.no_u8, self.no_q)
+            amax = self.q8_amax if self.q8 else self.empty
+            if self.q8 and not self._q8_cal[h]:
+                # the first step of this engine: one pass as step -1 only to record the gradient maxima
+                # the step-0 scales come from (its stores and partials are overwritten by the real one;
+                # the reference loss's mu_prev / v_prev writes are idempotent)
+                self.ext.mlp_head_train(*args, h, part_dw, *w8, amax, -1)
+                self._q8_cal[h] = True
+            self.ext.mlp_head_train(*args, h, part_dw, *w8, amax, self._q8_step)
         if h == 0 and idx_t is self.empty and not self.phead:
             self._xT_valid = True   # the policy kernel wrote x^T of this buffer (full batch)
-        if h == 0 and p.loss == "dppo_ref":
-            self.log_std_old.copy_(self.model.flat.data[:self.A])   # train.py:164, before Adam moves it
+        if h == 0:
+            self._keep_log_std()
 
     def _joint_heads(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
         """both head kernels into the shared partial buffer (disjoint columns and operands), in
@@ -1530,37 +1537,29 @@ class HipEngine:
                 self._flush_value()   # the previous step's value Adam (side stream) lands first
             self._head_kernel(h, idx_t, first, xt_ready, self.part_joint, self.part_dw_joint[h])
 
-    def _joint_grad(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
-        """both head kernels (one shared partial buffer), ONE wgrad over both heads' layers, ONE
-        gather of the whole gradient into grad_flat (no optimizer step)"""
+    def _joint(self, gather, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
+        """both head kernels (one shared partial buffer), ONE wgrad over both heads' layers, ONE ``gather`` launch
+        over the whole flat vector"""
         self._joint_heads(idx_t, first, xt_ready, xmode)
         b = self.joint_bucket
         self._wgrad(b, xmode)
-        src_off, src_meta = self.joint_src
-        rc, rd = self.items["joint"]
-        self.ext.grad_gather(b["slab"], src_off, src_meta, self.part_joint, self.nhead_blk, self.part_joint.shape[1],
-                             rc, rd, 1.0 / self.mb, self.grad_flat, self.loss_sums, b["runs"])
+        gather(b, *self.joint_src, self.part_joint, self.nhead_blk, self.items["joint"])
 
-    def _joint_step(self, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
-        """world size 1: policy kernel, value kernel (one shared partial buffer), ONE wgrad over
-        both heads' layers, ONE gather + Adam launch over the whole flat vector"""
-        self._joint_heads(idx_t, first, xt_ready, xmode)
-        b = self.joint_bucket
-        self._wgrad(b, xmode)
-        self._gather_adam(b, *self.joint_src, self.part_joint, self.nhead_blk, self.items["joint"])
+    def _joint_grad(self, *mbt) -> None:
+        """_joint ending in the gather of the whole gradient into grad_flat (no optimizer step)"""
+        self._joint(self._gather, *mbt)
+
+    def _joint_step(self, *mbt) -> None:
+        """world size 1: _joint ending in the gather + Adam launch"""
+        self._joint(self._gather_adam, *mbt)
 
     def _head_chain(self, h: int, idx_t, first: bool, xt_ready: bool, xmode: str) -> None:
         """head h's kernel -> its wgrad -> its gather into its flat range of grad_flat"""
-        M = self.mb
         self._head_kernel(h, idx_t, first, xt_ready, self.part_h[h], self.part_dw[h])
         b = self.buckets[h]
         self._wgrad(b, xmode)
-        lo, hi = self.head_range[h]
-        part = self.part_h[h]
-        rc, rd = self.items["policy" if h == 0 else "value"]
-        self.ext.grad_gather(b["slab"], self.src_off[lo:hi], self.src_meta[lo:hi], part, self.nhead_blk,
-                             part.shape[1], rc, rd, 1.0 / M, self.grad_flat[lo:hi], self.loss_sums,
-                             [r - lo for r in b["runs"]])
+        self._gather(b, self.src_off, self.src_meta, self.part_h[h], self.nhead_blk,
+                     self.items["policy" if h == 0 else "value"], *self.head_range[h])
 
     def _head_adam(self, h: int, step_no: int) -> None:
         """no-clip Adam over head h's flat range (after its all-reduce); its norm region"""
@@ -1589,6 +1588,15 @@ class HipEngine:
                       self.wimg, self.w_map[lo:hi], self.wt_map[lo:hi], self.dt, self.no_q, step_no,
                       *self._f8(lo, hi), self._gate_arg)
 
+    def _gather(self, b: Dict, src_off: torch.Tensor, src_meta: torch.Tensor, part: torch.Tensor, npblk: int, items,
+                lo: int = 0, hi: Optional[int] = None) -> None:
+        """the gather launch of bucket b into grad_flat; [lo, hi): into one head's slice of the flat vectors"""
+        grad, runs = self.grad_flat, b["runs"]
+        if hi is not None:          # (red_dst indexes the slice: the runs rebased to it)
+            src_off, src_meta, grad, runs = src_off[lo:hi], src_meta[lo:hi], grad[lo:hi], [r - lo for r in runs]
+        self.ext.grad_gather(b["slab"], src_off, src_meta, part, npblk, part.shape[1], *items, 1.0 / self.mb, grad,
+                             self.loss_sums, runs)
+
     def _gather_adam(self, b: Dict, src_off: torch.Tensor, src_meta: torch.Tensor, part: torch.Tensor, npblk: int,
                      items) -> None:
         """ONE whole optimizer step as the fused gather + no-clip Adam launch over bucket b (world size 1)"""
@@ -1605,54 +1613,37 @@ class HipEngine:
         """one minibatch gradient into grad_flat (no optimizer step; tests / the whole-vector
         path).  ``apply=True`` (one-kernel path, only when can_fuse_apply()): the gather and the
         Adam step run as ONE launch — the same update as grad() then apply()."""
-        if self.heads:
-            self._flush_value()
-            mbt = self._minibatch(idx)
-            if apply:
-                assert self.can_fuse_apply(), "fused gather + Adam is not available here"
-                self._joint_step(*mbt)
-            else:
-                self._heads_grad(*mbt)
+        self._flush_value()                     # (only the per-head chains leave a value step pending)
+        mbt = self._minibatch(idx)
+        if not apply:
+            self._grad_chain(*mbt)
             return None
-        idx_t, first, xt_ready, xmode = self._minibatch(idx)
-        if apply:
-            assert self.can_fuse_apply(), "fused gather + Adam is not available here"
-            self._launch_grad(idx_t, first, xt_ready, fused_apply=True)
+        assert self.can_fuse_apply(), "fused gather + Adam is not available here"
+        if self.heads:
+            self._joint_step(*mbt)
         else:
-            self._launch_grad(idx_t, first, xt_ready)
+            self._launch_grad(*mbt[:3], fused_apply=True)
         return None
 
     def _launch_grad(self, idx_t: torch.Tensor, first: bool, xt_ready: bool, fused_apply: bool = False) -> None:
-        p, M = self.p, self.mb
-        opts = [0 if p.loss == "ppo" else 1, 0 if p.value_loss == "mse" else 1,
-                1 if p.std_convention == "var" else 0, 1 if first else 0, self.npart]
-        fopts = [float(p.clip), float(p.ent_coeff)]
-        self.ext.mlp_train(self.dt, self.x_buf, idx_t, 0, M, self.wimg, self.layout, self.scales,
-                           self.model.flat.data, self.log_std_old, self.A, self.actions, self.logp, self.adv,
-                           self.ret, self.values_buf, self.mu_prev, self.v_prev, opts, fopts, self.tbufs,
-                           self.ldT, self.part, False, xt_ready, self.no_u8, self.no_q, self.empty, 0)
+        self.ext.mlp_train(*self._update_args(idx_t, first, xt_ready, self.part))
         b = self.buckets[0]
         self._wgrad(b, "fm")
+        gather = (b, self.src_off, self.src_meta, self.part, self.ntrain_blk, self.items["legacy"])
         if fused_apply:
-            if p.loss == "dppo_ref":   # train.py:164: the pre-update log_std, before Adam moves it
-                self.log_std_old.copy_(self.model.flat.data[:self.A])
-            self._gather_adam(b, self.src_off, self.src_meta, self.part, self.ntrain_blk, self.items["legacy"])
-            return
-        rc, rd = self.items["legacy"]
-        self.ext.grad_gather(b["slab"], self.src_off, self.src_meta, self.part, self.ntrain_blk, self.npart,
-                             rc, rd, 1.0 / M, self.grad_flat, self.loss_sums, b["runs"])
-        if p.loss == "dppo_ref":
-            self.log_std_old.copy_(self.model.flat.data[:self.A])  # train.py:164
+            self._keep_log_std()        # (before the fused Adam moves it)
+            self._gather_adam(*gather)
+        else:
+            self._gather(*gather)
+            self._keep_log_std()
 
     @torch.no_grad()
     def apply(self, extra_grad: float = 0.0) -> None:
         """whole-vector Adam (+ clip) after grad() [+ the all-reduce]"""
-        p = self.p
         self._flush_value()
         if extra_grad:
             self.grad_flat.add_(extra_grad)
-        mx = float(p.max_grad_norm) if (p.max_grad_norm is not None and p.max_grad_norm > 0) else 0.0
-        self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_whole], mx, self._next_step())
+        self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_whole], self.max_norm, self._next_step())
         self._stepped(self.norm_n_whole)
 
     def pack_metrics(self, ep2: torch.Tensor) -> Optional[torch.Tensor]:
@@ -1690,7 +1681,7 @@ class HipEngine:
         into host memory by the worker without a sync (``losses_from_vector`` decodes it)."""
         if self._loss_dev is None:
             return None
-        if self.p.max_grad_norm is not None and self.p.max_grad_norm > 0:
+        if self.max_norm:
             gn = self.adam_state[2:3]              # the clip pass computed it
         else:                                      # no-clip Adam skips the norm: last step's gradient
             gn = torch.linalg.vector_norm(self.grad_flat).reshape(1)
