@@ -992,13 +992,22 @@ const float* gate_ptr(const torch::Tensor& gate) {
   return gate.data_ptr<float>();
 }
 
+// lr_schedule adaptive's lr_state f32[4] = [lr, downs, ups, reserved] (csrc/kernels.h LrAdapt)
+float* lr_state_ptr(const torch::Tensor& t) {
+  check(t, "lr_state", at::kFloat, 4);
+  TORCH_CHECK(t.numel() == 4, "lr_state is [lr, downs, ups, reserved]");
+  return t.data_ptr<float>();
+}
+
 // AdamArgs (csrc/kernels.h) of one optimizer launch over the flat range p, checked.  host_step >= 1: the step
 // number of this update (eager launch: one fused kernel when there is no clipping); 0: read the device counter
 // (graph replay).  gate: an empty tensor is the ungated launch; else target_kl's gated step — applied only while
-// gate[0] == 0, the step number state[0] + 1 read on the device (host_step unused).
+// gate[0] == 0, the step number state[0] + 1 read on the device (host_step unused).  lr_dev: none or an empty tensor
+// is the host rate lr; else lr_schedule adaptive's lr_state f32[4], whose slot 0 the gated form reads (lr unused).
+using OptT = const std::optional<torch::Tensor>&;
 AdamArgs adam_args(CT p, CT g, CT m, CT v, double lr, double b1, double b2, double eps, double max_norm,
                    int64_t host_step, CT state, CT norm_part, CT wimg, CT w_map, CT wt_map, int64_t dt, CT qmul,
-                   CT f8_img, CT f8_lid, CT f8_qs, CT gate) {
+                   CT f8_img, CT f8_lid, CT f8_qs, CT gate, OptT lr_dev) {
   const int64_t n = p.numel();
   check(p, "p", at::kFloat, n);
   check(g, "g", at::kFloat, n);
@@ -1033,6 +1042,10 @@ AdamArgs adam_args(CT p, CT g, CT m, CT v, double lr, double b1, double b2, doub
   a.f8 = f8_shadow(f8_img, f8_lid, f8_qs, n);
   if (gate.defined() && gate.numel() > 0) a.gate = gate_ptr(gate);
   a.host_step = a.gate != nullptr ? 0 : (int)host_step;
+  if (lr_dev.has_value() && lr_dev->defined() && lr_dev->numel() > 0) {
+    TORCH_CHECK(a.gate != nullptr, "lr_dev needs a gate: only the gated launches read the rate on the device");
+    a.lr_dev = lr_state_ptr(*lr_dev);
+  }
   return a;
 }
 
@@ -1041,20 +1054,34 @@ AdamArgs adam_args(CT p, CT g, CT m, CT v, double lr, double b1, double b2, doub
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, double lr, double b1, double b2,
           double eps, double max_norm, torch::Tensor state, torch::Tensor norm_part, torch::Tensor wimg,
           torch::Tensor w_map, torch::Tensor wt_map, int64_t dt, torch::Tensor qmul, int64_t host_step,
-          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs, torch::Tensor gate) {
+          torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs, torch::Tensor gate, OptT lr_dev) {
   launch_adam(adam_args(p, g, m, v, lr, b1, b2, eps, max_norm, host_step, state, norm_part, wimg, w_map, wt_map, dt,
-                        qmul, f8_img, f8_lid, f8_qs, gate),
+                        qmul, f8_img, f8_lid, f8_qs, gate, lr_dev),
               cur_stream());
   after_launch(__func__);
 }
 
-// target_kl: the gate after a step (csrc/optim.hip kl_gate_kernel; ops/oracle.py kl_gate)
-void kl_gate(torch::Tensor loss_sums, torch::Tensor gate, torch::Tensor state, double target_kl) {
+// target_kl: the gate after a step (csrc/optim.hip kl_gate_kernel; ops/oracle.py kl_gate).  lr_state: none or an
+// empty tensor is the gate alone (the other rate operands unread); else lr_schedule adaptive's rate block
+// (ops/oracle.py lr_adapt)
+void kl_gate(torch::Tensor loss_sums, torch::Tensor gate, torch::Tensor state, double target_kl, OptT lr_state,
+             double kl_target, double factor, double lr_min, double lr_max) {
   check(loss_sums, "loss_sums", at::kFloat, 8);
   check(state, "state", at::kFloat, 4);
   TORCH_CHECK(target_kl > 0, "kl_gate needs target_kl > 0");
+  LrAdapt ra{};
+  if (lr_state.has_value() && lr_state->defined() && lr_state->numel() > 0) {
+    ra.lr_state = lr_state_ptr(*lr_state);
+    TORCH_CHECK(kl_target > 0 && std::isfinite(kl_target), "kl_gate's rate block needs a finite kl_target > 0");
+    TORCH_CHECK(factor > 1 && std::isfinite(factor), "kl_gate's rate block needs a finite factor > 1");
+    TORCH_CHECK(lr_min > 0 && lr_min <= lr_max && std::isfinite(lr_max), "kl_gate's rate block needs 0 < lr_min <= lr_max");
+    ra.kl_target = (float)kl_target;
+    ra.factor = (float)factor;
+    ra.lr_min = (float)lr_min;
+    ra.lr_max = (float)lr_max;
+  }
   launch_kl_gate(loss_sums.data_ptr<float>(), const_cast<float*>(gate_ptr(gate)), state.data_ptr<float>(),
-                 (float)target_kl, cur_stream());
+                 (float)target_kl, ra, cur_stream());
   after_launch(__func__);
 }
 
@@ -1068,9 +1095,9 @@ void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_me
                  torch::Tensor v, double lr, double b1, double b2, double eps, int64_t step, torch::Tensor state,
                  torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map, torch::Tensor wt_map, int64_t dt,
                  torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs,
-                 torch::Tensor gate) {
+                 torch::Tensor gate, OptT lr_dev) {
   const AdamArgs a = adam_args(p, g, m, v, lr, b1, b2, eps, 0.0, step, state, norm_part, wimg, w_map, wt_map, dt, qmul,
-                               f8_img, f8_lid, f8_qs, gate);
+                               f8_img, f8_lid, f8_qs, gate, lr_dev);
   const GatherArgs ga =
       gather_args(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, p.numel());
   TORCH_CHECK(a.gate != nullptr || step >= 1, "gather_adam needs the host step number (eager launches only)");
@@ -1172,9 +1199,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("obs_merge", &obs_merge);
   m.def("obs_observe", &obs_observe);
   m.def("obs_moments_nblk", &obs_moments_nblk);
-  m.def("adam", &adam);
-  m.def("gather_adam", &gather_adam);
-  m.def("kl_gate", &kl_gate);
+  // (the trailing operands of lr_schedule adaptive have defaults: every earlier call keeps its argument list)
+  namespace py = pybind11;
+  m.def("adam", &adam, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("max_norm"), py::arg("state"), py::arg("norm_part"), py::arg("wimg"),
+        py::arg("w_map"), py::arg("wt_map"), py::arg("dt"), py::arg("qmul"), py::arg("host_step"), py::arg("f8_img"),
+        py::arg("f8_lid"), py::arg("f8_qs"), py::arg("gate"), py::arg("lr_dev") = py::none());
+  m.def("gather_adam", &gather_adam, py::arg("slab"), py::arg("src_off"), py::arg("src_meta"), py::arg("part"),
+        py::arg("npblk"), py::arg("npart"), py::arg("red_col"), py::arg("red_dst"), py::arg("runs"), py::arg("scale"),
+        py::arg("loss_out"), py::arg("g"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("step"), py::arg("state"), py::arg("norm_part"), py::arg("wimg"),
+        py::arg("w_map"), py::arg("wt_map"), py::arg("dt"), py::arg("qmul"), py::arg("f8_img"), py::arg("f8_lid"),
+        py::arg("f8_qs"), py::arg("gate"), py::arg("lr_dev") = py::none());
+  m.def("kl_gate", &kl_gate, py::arg("loss_sums"), py::arg("gate"), py::arg("state"), py::arg("target_kl"),
+        py::arg("lr_state") = py::none(), py::arg("kl_target") = 0.0, py::arg("factor") = 0.0,
+        py::arg("lr_min") = 0.0, py::arg("lr_max") = 0.0);
   m.def("pack", &pack);
   m.def("debug_invalid_launch", &debug_invalid_launch);
   m.def("fp8_refresh", &fp8_refresh);

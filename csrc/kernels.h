@@ -311,6 +311,17 @@ struct AdamArgs {
   // is the only writer of gate and, in gated mode, of both.  A stopped launch (gate[0] != 0) still
   // writes the gradient, the loss sums, norm_part and state[2]; p, m, v and the images stay.
   const float* gate;
+  // lr_schedule adaptive (docs/ARCHITECTURE.md §23): null is the host rate lr; else the rate is
+  // lr_state[0], read on the device by the gated form (lr unread).  Needs gate.
+  const float* lr_dev;
+};
+
+// lr_schedule adaptive: the rate block of launch_kl_gate.  lr_state f32[4] = [lr, downs, ups, reserved]
+// (the counts cumulative); null lr_state: no adaptation, the rest unread.  After an applied step,
+// kl > 2 * kl_target: lr = max(lr / factor, lr_min); kl < kl_target / 2: lr = min(lr * factor, lr_max).
+struct LrAdapt {
+  float* lr_state;
+  float kl_target, factor, lr_min, lr_max;
 };
 
 struct WgradTask {
@@ -381,8 +392,9 @@ void launch_adam(const AdamArgs& a, hipStream_t s);
 // grad_gather + no-clip Adam in one launch: world size 1 only (no all-reduce between them); a.nblk
 // must exceed item_blocks(ga.nitems), and ungated it needs a.host_step >= 1
 void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipStream_t s);
-// target_kl: the gate after a step (AdamArgs::gate)
-void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s);
+// target_kl: the gate after a step (AdamArgs::gate); ra: the adaptive rate's block (null lr_state: none)
+void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, const LrAdapt& ra,
+                    hipStream_t s);
 void launch_pack(const float* p, int n, void* wimg, const int* w_map, const int* wt_map, int dt,
                  const float* img_scale, hipStream_t s);
 // fp8 forward image: qscale[6] = per-layer amax / 416 of p (lid: layer of each parameter, -1

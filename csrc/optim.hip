@@ -191,12 +191,19 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
 // still does every write that is not p, m, v, a weight image, the e4m3 shadow or the counter (the
 // gradient, the loss sums, the sum-of-squares partials, state[2]).  !GATE takes an empty argument
 // and is the kernel without any of it.
-template <bool GATE> struct KlGate { const float* gate; };
+// lr_schedule adaptive (docs/ARCHITECTURE.md §23): lr null is the host float; else lr_state[0], read
+// like the step counter — once per workgroup, written by kl_gate_kernel alone in its own launch.
+template <bool GATE> struct KlGate { const float* gate; const float* lr; };
 template <> struct KlGate<false> {};
 template <bool GATE>
 DEV bool kl_stopped(const KlGate<GATE>& kg) {
   if constexpr (GATE) return kg.gate[0] != 0.f;
   else return false;
+}
+template <bool GATE>
+DEV float kl_lr(const KlGate<GATE>& kg, float lr) {
+  if constexpr (GATE) return kg.lr != nullptr ? kg.lr[0] : lr;
+  else return lr;
 }
 
 template <bool GATE = false>
@@ -243,7 +250,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const float step = GATE ? state[0] + 1.f : state[1];
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
-  const float step_size = lr / bc1;
+  const float step_size = kl_lr(kg, lr) / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
   const int i_end = kl_stopped(kg) ? 0 : n;   // (stopped: no element moves)
   for (int i = blockIdx.x * 256 + threadIdx.x; i < i_end; i += gridDim.x * 256) {
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p,
   const bool stop = kl_stopped(kg);
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
-  const float step_size = lr / bc1;
+  const float step_size = kl_lr(kg, lr) / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
   float ss = 0.f;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
   const bool stop = kl_stopped(kg);
   const float bc1 = 1.f - powf(b1, step);
   const float bc2 = 1.f - powf(b2, step);
-  const float step_size = lr / bc1;
+  const float step_size = kl_lr(kg, lr) / bc1;
   const float rbc2 = 1.f / sqrtf(bc2);
   const int nrb = item_blocks(nitems);   // reduce blocks
   float ss = 0.f;
@@ -433,8 +440,12 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
 // of gate and, in gated mode, of the step counter: if the step just enqueued was applied (stop was
 // 0) the counter advances; then kl = fl32(sums[3] / max(sums[5], 1)) of that step's loss sums is
 // held against the target.  !(kl <= target), so a NaN trips too; a set stop stays set.
+// lr_schedule adaptive (ops/oracle.py lr_adapt): with a rate block, the same thread is the only writer
+// of lr_state = [lr, downs, ups, reserved] — after an APPLIED step its kl moves the rate the next
+// step's Adam launches read (a stopped step's kl is the previous step's: adapting on it would
+// compound).  A NaN kl fails both comparisons.  A null block: the kernel without it.
 __global__ __launch_bounds__(64) void kl_gate_kernel(const float* __restrict__ sums, float* __restrict__ gate,
-                                                     float* __restrict__ state, float target) {
+                                                     float* __restrict__ state, float target, LrAdapt ra) {
   if (threadIdx.x != 0) return;
   const bool open = gate[0] == 0.f;
   if (open) {
@@ -448,6 +459,16 @@ __global__ __launch_bounds__(64) void kl_gate_kernel(const float* __restrict__ s
   if (open && !(kl <= target)) {
     gate[0] = 1.f;
     gate[2] = kl;
+  }
+  if (open && ra.lr_state != nullptr) {
+    const float lr = ra.lr_state[0];
+    if (kl > 2.f * ra.kl_target) {
+      ra.lr_state[0] = fmaxf(__fdiv_rn(lr, ra.factor), ra.lr_min);
+      ra.lr_state[1] += 1.f;
+    } else if (kl < 0.5f * ra.kl_target) {
+      ra.lr_state[0] = fminf(__fmul_rn(lr, ra.factor), ra.lr_max);
+      ra.lr_state[2] += 1.f;
+    }
   }
 }
 
@@ -669,11 +690,16 @@ extern "C" void set_adam_fused(int on) { g_adam_fused = on; }
 
 namespace {
 // f(integral_constant<int, DT>, KlGate<GATE>): the image's precision and, from a.gate, the gated
-// or the ungated form of an Adam launch
+// or the ungated form of an Adam launch (the gated one with the host rate or, from a.lr_dev, the
+// device rate).  A device rate without a gate has no form: refused, nothing is launched.
 template <typename F>
 void dispatch_adam(const AdamArgs& a, F&& f) {
+  if (a.gate == nullptr && a.lr_dev != nullptr) {
+    dppo_note_error(hipErrorInvalidValue, __FILE__, __LINE__);
+    return;
+  }
   dispatch_dt(a.dt, [&](auto d) {
-    if (a.gate != nullptr) f(d, KlGate<true>{a.gate});
+    if (a.gate != nullptr) f(d, KlGate<true>{a.gate, a.lr_dev});
     else f(d, KlGate<false>{});
   });
 }
@@ -713,8 +739,9 @@ extern "C" void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipS
   HIP_CHECK_LAUNCH();
 }
 
-extern "C" void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, hipStream_t s) {
-  hipLaunchKernelGGL(kl_gate_kernel, dim3(1), dim3(64), 0, s, loss_sums, gate, state, target_kl);
+extern "C" void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, const LrAdapt& ra,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(kl_gate_kernel, dim3(1), dim3(64), 0, s, loss_sums, gate, state, target_kl, ra);
   HIP_CHECK_LAUNCH();
 }
 

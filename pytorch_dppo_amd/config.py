@@ -86,6 +86,17 @@ class Params:
                                          # decision is taken on the device).  Stopped steps still run their gradient
                                          # kernels: no time is saved.  0: off.  Refused with loss=dppo_ref, compat,
                                          # overlap_rollout and overlap_value_epochs.
+    lr_schedule: str = "constant"        # constant | linear (annealed per iteration to lr * lr_final_frac at the end
+                                         # of the run: needs max_iters or total_env_steps) | adaptive (after every applied
+                                         # step the rate is divided by lr_adapt_factor when that step's KL is above
+                                         # 2 * lr_kl_target and multiplied by it when below half, inside [lr_min, lr_max];
+                                         # ops/oracle.lr_adapt, decided and read on the device).  adaptive is refused with
+                                         # loss=dppo_ref, compat, overlap_rollout and overlap_value_epochs.
+    lr_final_frac: float = 0.0           # linear: the rate at the run's last iteration, as a fraction of lr
+    lr_kl_target: float = 0.008          # adaptive: the KL the rate is steered to
+    lr_adapt_factor: float = 1.5         # adaptive: the divisor / multiplier (> 1)
+    lr_min: float = 1e-6                 # adaptive: the rate's bounds; lr starts inside them
+    lr_max: float = 1e-2
     minibatches_per_epoch: int = 0       # 0 = buffer // batch_size (full pass); reference ppo.py uses 1
     total_env_steps: int = 0             # 0 = unbounded (use max_iters)
     max_iters: int = 0                   # 0 = unbounded
@@ -227,6 +238,53 @@ class Params:
                 raise ValueError("target_kl cannot be combined with overlap_rollout / overlap_value_epochs: they move "
                                  "a value step to a side stream or behind the next rollout, and a gated step reads and "
                                  "advances one device counter in stream order")
+
+        if self.lr_schedule not in ("constant", "linear", "adaptive"):
+            raise ValueError(f"lr_schedule must be constant|linear|adaptive, got {self.lr_schedule}")
+        if self.lr_schedule == "linear":
+            if not (self.max_iters > 0 or self.total_env_steps > 0):
+                raise ValueError("lr_schedule=linear anneals to the end of the run: set max_iters or total_env_steps")
+            if not 0.0 <= float(self.lr_final_frac) <= 1.0:
+                raise ValueError(f"lr_final_frac must be in [0, 1], got {self.lr_final_frac}")
+        if self.lr_schedule == "adaptive":
+            if not self.lr_kl_target > 0:
+                raise ValueError(f"lr_kl_target must be > 0, got {self.lr_kl_target}")
+            if not self.lr_adapt_factor > 1:
+                raise ValueError(f"lr_adapt_factor must be > 1, got {self.lr_adapt_factor}")
+            if not 0 < self.lr_min <= self.lr_max:
+                raise ValueError(f"lr_schedule=adaptive needs 0 < lr_min <= lr_max, got [{self.lr_min}, {self.lr_max}]")
+            if not self.lr_min <= self.lr <= self.lr_max:
+                raise ValueError(f"lr_schedule=adaptive: the initial lr {self.lr} is outside [lr_min, lr_max] = "
+                                 f"[{self.lr_min}, {self.lr_max}]")
+            if self.loss == "dppo_ref":
+                raise ValueError("lr_schedule=adaptive cannot be combined with loss=dppo_ref: that loss reports "
+                                 "approx_kl = 0 by construction, so the rate would only ever go up")
+            if self.compat:
+                raise ValueError("lr_schedule=adaptive cannot be combined with compat: compat reproduces the reference, "
+                                 "whose rate is constant")
+            if self.overlap_rollout or self.overlap_value_epochs:
+                raise ValueError("lr_schedule=adaptive cannot be combined with overlap_rollout / overlap_value_epochs: "
+                                 "they move a value step to a side stream or behind the next rollout, and an adaptive "
+                                 "step reads the device rate and counter in stream order")
+
+    def gated(self) -> bool:
+        """the update steps run through the KL gate (target_kl, or the adaptive rate, which lives behind it)"""
+        return self.target_kl > 0 or self.lr_schedule == "adaptive"
+
+    def gate_target(self) -> float:
+        """the KL the gate trips on: target_kl, else +inf (lr_schedule=adaptive alone: only a NaN KL trips)"""
+        return float(self.target_kl) if self.target_kl > 0 else float("inf")
+
+    def schedule_iters(self, world_size: int = 1) -> int:
+        """the run's iteration count n of lr_schedule=linear: max_iters, else the iterations total_env_steps takes"""
+        if self.max_iters > 0:
+            return int(self.max_iters)
+        return max(1, -(-int(self.total_env_steps) // (self.buffer_rows * max(1, world_size))))
+
+    def linear_lr(self, iteration: int, world_size: int = 1) -> float:
+        """lr_schedule=linear: the rate of iteration ``iteration`` (0-based), a pure function of the index"""
+        n = self.schedule_iters(world_size)
+        return self.lr * (1.0 - (1.0 - self.lr_final_frac) * min(iteration, n) / n)
 
     def heartbeat_interval(self, world_size: int) -> float:
         """the heartbeat period in effect: heartbeat_s, or 5 s (auto) whenever there are peers"""

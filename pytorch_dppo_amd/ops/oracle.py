@@ -237,6 +237,34 @@ def kl_gate(kl_sum, count, target_kl: float, gate) -> Tuple[list, bool]:
     return [stop, applied_n, trip, kl], applied
 
 
+def lr_adapt(lr, kl, kl_target: float, factor: float, lr_min: float, lr_max: float) -> float:
+    """``lr_schedule=adaptive``: the rate after one APPLIED step whose KL was ``kl`` (the twin of the rate
+    block of ``csrc/optim.hip`` kl_gate_kernel; ``kl`` is ``kl_gate``'s ``last_kl``, an fp32 value)::
+
+        if   kl > fl32(2 * kl_target):    lr = max(fl32(lr / factor), lr_min)
+        elif kl < fl32(0.5 * kl_target):  lr = min(fl32(lr * factor), lr_max)
+
+    otherwise unchanged; a NaN ``kl`` fails both comparisons.  The caller does not call it for a step
+    that was not applied (the gate was already stopped): the parameters did not move, its KL is the
+    previous step's, and the rule would compound.  Every operand is rounded to fp32 first, as the
+    kernel receives it; returns the new rate as a python float holding an fp32 value."""
+    f32 = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(())   # noqa: E731
+    lr, kl, t, fac = f32(lr), f32(kl), f32(kl_target), f32(factor)
+    if bool(kl > f32(2.0) * t):
+        return float(torch.maximum(lr / fac, f32(lr_min)))
+    if bool(kl < f32(0.5) * t):
+        return float(torch.minimum(lr * fac, f32(lr_max)))
+    return float(lr)
+
+
+def lr_adapt_dir(kl, kl_target: float) -> int:
+    """the branch ``lr_adapt`` takes: -1 down, +1 up, 0 unchanged (the cumulative ``lr_downs`` / ``lr_ups``
+    count the branches, a clamped one included)"""
+    f32 = lambda x: torch.as_tensor(x, dtype=torch.float32).reshape(())   # noqa: E731
+    kl, t = f32(kl), f32(kl_target)
+    return -1 if bool(kl > f32(2.0) * t) else (1 if bool(kl < f32(0.5) * t) else 0)
+
+
 def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,
                lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
     """torch.optim.Adam (default, non-amsgrad, no weight decay) on flat buffers."""

@@ -298,7 +298,19 @@ class HipEngine:
         # so that a gated step's one collective sums both over the ranks.  Only with the flag on.
         self.gate: Optional[torch.Tensor] = None
         self._grad_sums: Optional[torch.Tensor] = None
-        if float(getattr(params, "target_kl", 0.0)) > 0:
+        # lr_schedule (§23): lr is the host rate of the Adam launches (linear: the worker sets it once per
+        # iteration, before begin_update()).  adaptive: the rate lives in lr_state = [lr, downs, ups,
+        # reserved], read by the gated Adam launches and written by the kl_gate launch alone — the steps
+        # take _gated_step whether or not target_kl is set.  Allocated only under adaptive.
+        self.lr = float(params.lr)
+        self.lr_state: Optional[torch.Tensor] = None
+        self._rate_block: tuple = ()         # kl_gate's trailing operands
+        if params.lr_schedule == "adaptive":
+            self.lr_state = torch.tensor([self.lr, 0.0, 0.0, 0.0], **f32)
+            self._rate_block = (self.lr_state, float(params.lr_kl_target), float(params.lr_adapt_factor),
+                                float(params.lr_min), float(params.lr_max))
+        self._gate_target = float(params.gate_target())
+        if params.gated():
             self.gate = torch.zeros(4, **f32)
             self._grad_sums = torch.zeros(n + NPART_FIXED, **f32)
             self.grad_flat = self._grad_sums[:n]
@@ -342,6 +354,7 @@ class HipEngine:
         self.empty = torch.empty(0, dtype=torch.int32, **dev)
         self.no_q = torch.empty(0, **f32)
         self._gate_arg = self.no_q if self.gate is None else self.gate    # the Adam bindings' gate (empty: ungated)
+        self._lr_arg = self.no_q if self.lr_state is None else self.lr_state    # ... and lr_dev (empty: the host rate)
         self.no_u8 = torch.empty(0, dtype=torch.uint8, **dev)
         self._first_step = True
         self._loss_dev: Optional[torch.Tensor] = None
@@ -411,8 +424,11 @@ class HipEngine:
         # [stop, applied, trip_kl, applied since the start of training] (target_kl)
         self._m_ret = 2 + NPART_FIXED + 1
         self._m_gate = self._m_ret + (1 if self.ret_stats is not None else 0)
-        if self.gate is not None:
-            self.metrics_buf = torch.zeros(self._m_gate + 4, dtype=torch.float64, **dev)
+        # ... then lr_schedule's [lr, downs, ups] (adaptive) or [lr] (linear)
+        self._m_lr = self._m_gate + (4 if self.gate is not None else 0)
+        n_lr = {"constant": 0, "linear": 1, "adaptive": 3}[params.lr_schedule]
+        if self.gate is not None or n_lr:
+            self.metrics_buf = torch.zeros(self._m_lr + n_lr, dtype=torch.float64, **dev)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -1410,7 +1426,8 @@ class HipEngine:
         self._norm_n = self.norm_regions[1][1]
 
     def _gated_step(self, idx: Optional[torch.Tensor], extra_grad: float, allreduce, mean: bool) -> None:
-        """step() under target_kl (docs/ARCHITECTURE.md §22): the gradient kernels always run; the Adam
+        """step() under target_kl and / or lr_schedule=adaptive (docs/ARCHITECTURE.md §22, §23; adaptive: the
+        Adam launch reads the rate lr_state[0] and kl_gate moves it): the gradient kernels always run; the Adam
         launch is the gated form (applied while gate[0] == 0, step number adam_state[0] + 1 read on the
         device); the kl_gate launch ends the step.  World size 1 with can_fuse_apply: the joint gather +
         Adam launch, gated.  Everything else: ONE gather of the whole gradient, ONE all-reduce of
@@ -1430,7 +1447,7 @@ class HipEngine:
                 else:
                     self._reduce_wait(allreduce(self._grad_sums), self._grad_sums, mean)
             self.apply(extra_grad)
-        self.ext.kl_gate(self.loss_sums, self.gate, self.adam_state, float(self.p.target_kl))
+        self.ext.kl_gate(self.loss_sums, self.gate, self.adam_state, self._gate_target, *self._rate_block)
 
     def _split_step_side(self, allreduce) -> None:
         """the joint gradient is gathered: the value range's all-reduce (the side communicator) +
@@ -1584,9 +1601,9 @@ class HipEngine:
         p = self.p
         b1, b2 = p.adam_betas
         self.ext.adam(self.model.flat.data[lo:hi], self.grad_flat[lo:hi], self.adam_m[lo:hi], self.adam_v[lo:hi],
-                      float(p.lr), float(b1), float(b2), float(p.adam_eps), max_norm, self.adam_state, norm_part,
+                      float(self.lr), float(b1), float(b2), float(p.adam_eps), max_norm, self.adam_state, norm_part,
                       self.wimg, self.w_map[lo:hi], self.wt_map[lo:hi], self.dt, self.no_q, step_no,
-                      *self._f8(lo, hi), self._gate_arg)
+                      *self._f8(lo, hi), self._gate_arg, self._lr_arg)
 
     def _gather(self, b: Dict, src_off: torch.Tensor, src_meta: torch.Tensor, part: torch.Tensor, npblk: int, items,
                 lo: int = 0, hi: Optional[int] = None) -> None:
@@ -1604,9 +1621,9 @@ class HipEngine:
         b1, b2 = p.adam_betas
         self.ext.gather_adam(b["slab"], src_off, src_meta, part, npblk, part.shape[1], *items, b["runs"],
                              1.0 / self.mb, self.loss_sums, self.grad_flat, self.model.flat.data, self.adam_m,
-                             self.adam_v, float(p.lr), float(b1), float(b2), float(p.adam_eps), self._next_step(),
+                             self.adam_v, float(self.lr), float(b1), float(b2), float(p.adam_eps), self._next_step(),
                              self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map,
-                             self.dt, self.no_q, *self._f8(), self._gate_arg)
+                             self.dt, self.no_q, *self._f8(), self._gate_arg, self._lr_arg)
         self._stepped(self.norm_n_whole)
 
     def grad(self, idx: Optional[torch.Tensor], apply: bool = False) -> None:
@@ -1674,7 +1691,23 @@ class HipEngine:
                 g0 = self._m_gate
                 self.metrics_buf[g0:g0 + 3].copy_(self.gate[:3])
                 self.metrics_buf[g0 + 3:g0 + 4].copy_(self.adam_state[0:1])
+            if self.lr_state is not None:       # [lr, downs, ups] behind the gate tail
+                self.metrics_buf[self._m_lr:self._m_lr + 3].copy_(self.lr_state[:3])
+            elif self.metrics_buf.numel() > self._m_lr:     # linear: the iteration's host rate
+                self.metrics_buf[self._m_lr:].fill_(self.lr)
         return self.metrics_buf
+
+    def lr_tail(self) -> torch.Tensor:
+        """the metrics vector's rate slots where pack_metrics does not run: [lr, downs, ups] (adaptive) or [lr]"""
+        if self.lr_state is not None:
+            return self.lr_state[:3]
+        return torch.tensor([self.lr], dtype=torch.float64)
+
+    def lr_state_dict(self) -> torch.Tensor:
+        return self.lr_state.detach().cpu()
+
+    def load_lr_state(self, t: torch.Tensor) -> None:
+        self.lr_state.copy_(t.to(self.lr_state.device, torch.float32))
 
     def loss_vector(self) -> Optional[torch.Tensor]:
         """device [loss sums of the last minibatch (8) | grad norm of the last Adam step] — staged

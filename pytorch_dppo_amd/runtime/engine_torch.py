@@ -73,8 +73,16 @@ class TorchEngine:
         self.adam_step = 0
         # target_kl: [stop, applied, trip_kl, last_kl] of the current iteration (ops/oracle.kl_gate) and
         # the last step's (KL sum, row count); only with the flag on
-        self.gate: Optional[list] = [0.0, 0.0, 0.0, 0.0] if params.target_kl > 0 else None
+        self.gate: Optional[list] = [0.0, 0.0, 0.0, 0.0] if params.gated() else None
         self.kl_pair: Optional[torch.Tensor] = None
+        # lr_schedule: the rate apply() reads.  linear: the worker sets it once per iteration; adaptive:
+        # lr_state = [lr, downs, ups, reserved] as fp32 values (the HIP engine's device state), moved by
+        # adapt() after every applied step and never reset
+        self.lr = float(params.lr)
+        self.lr_state: Optional[list] = None
+        if params.lr_schedule == "adaptive":
+            self.lr = float(torch.tensor(params.lr, dtype=torch.float32))
+            self.lr_state = [self.lr, 0.0, 0.0, 0.0]
         self.flat_old = model.flat.detach().clone()  # dppo_ref "model_old" (train.py:128-129,164)
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.obs = env.reset().to(device)
@@ -260,9 +268,30 @@ class TorchEngine:
             oracle.clip_grad_norm_(g, self.p.max_grad_norm)
         self.adam_step += 1
         oracle.adam_step_(self.model.flat.data, g, self.adam_m, self.adam_v, self.adam_step,
-                          self.p.lr, self.p.adam_betas, self.p.adam_eps)
+                          self.lr, self.p.adam_betas, self.p.adam_eps)
         self._norm = norm
         return norm
+
+    def adapt(self, kl: float) -> None:
+        """lr_schedule=adaptive, after an APPLIED step whose KL was ``kl`` (the gate's last_kl):
+        ops/oracle.lr_adapt moves the rate the next step runs at"""
+        p, st = self.p, self.lr_state
+        st[0] = oracle.lr_adapt(st[0], kl, p.lr_kl_target, p.lr_adapt_factor, p.lr_min, p.lr_max)
+        d = oracle.lr_adapt_dir(kl, p.lr_kl_target)
+        if d:
+            st[1 if d < 0 else 2] += 1.0
+        self.lr = st[0]
+
+    def lr_tail(self) -> torch.Tensor:
+        """the metrics vector's rate slots: [lr, downs, ups] (adaptive) or [lr]"""
+        return torch.tensor(self.lr_state[:3] if self.lr_state is not None else [self.lr], dtype=torch.float64)
+
+    def lr_state_dict(self) -> torch.Tensor:
+        return torch.tensor(self.lr_state, dtype=torch.float32)
+
+    def load_lr_state(self, t: torch.Tensor) -> None:
+        self.lr_state = [float(x) for x in t.to(torch.float32).tolist()]
+        self.lr = self.lr_state[0]
 
     def last_losses(self) -> Dict[str, float]:
         out = dict(getattr(self, "_last", {}))

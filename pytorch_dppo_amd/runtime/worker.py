@@ -184,10 +184,16 @@ class DPPOWorker:
         eng.gae()
         tm.stop("values_gae")
         tm.start("update")
+        if p.lr_schedule == "linear":
+            # a pure function of the iteration index.  Set here, after flush_pending() / values(): every
+            # Adam launch of the previous iteration (a deferred value step, the CPU engine's deferred
+            # whole step) is enqueued by now, at the previous rate (docs/ARCHITECTURE.md §23)
+            eng.lr = p.linear_lr(self.iteration, self.ctx.world_size)
         eng.begin_update()
         N, mb, nmb = self._minibatch_plan()
         mean = p.grad_reduce == "mean"
-        gated = p.target_kl > 0
+        gated = p.gated()
+        adaptive = p.lr_schedule == "adaptive"
         self._perm_gen.manual_seed((p.seed * 1000003 + self.ctx.rank * 7919 + self.iteration) & 0x7FFFFFFF)
         for epoch in range(p.num_epoch):
             if mb >= N and nmb == 1:
@@ -233,7 +239,9 @@ class DPPOWorker:
                         self.updates += 1
                     else:
                         eng.skip()
-                    eng.gate, _ = oracle.kl_gate(pair[0], pair[1], p.target_kl, eng.gate)
+                    eng.gate, applied = oracle.kl_gate(pair[0], pair[1], p.gate_target(), eng.gate)
+                    if adaptive and applied:
+                        eng.adapt(eng.gate[3])         # the next step's rate (ops/oracle.lr_adapt)
                     continue
                 if deferred:
                     work = self.ctx.allreduce_grads(eng.grad_flat, async_op=True)
@@ -289,12 +297,14 @@ class DPPOWorker:
             flat, loss_dev = self._stage_parts(ro)
             if self.p.reward_norm:     # return_std rides behind the vector (pack_metrics wrote its own)
                 flat = torch.cat([flat, eng.ret_stats.std().to(flat.device)])
-            if self.p.target_kl > 0:   # [stop, applied, trip_kl | steps applied since the start], likewise
+            if self.p.gated():         # [stop, applied, trip_kl | steps applied since the start], likewise
                 if torch.is_tensor(eng.gate):      # (the GPU engine without a device rollout's ep2)
                     tail = torch.cat([eng.gate[:3], eng.adam_state[0:1]])
                 else:
                     tail = torch.tensor(list(eng.gate[:3]) + [float(self.updates)], dtype=torch.float64)
                 flat = torch.cat([flat, tail.to(flat.device, torch.float64)])
+            if self.p.lr_schedule != "constant":   # [lr, downs, ups] (adaptive) or [lr] (linear), behind the gate tail
+                flat = torch.cat([flat, eng.lr_tail().to(flat.device, torch.float64)])
         if dev.type == "cuda":
             # the stream the metrics were packed on (the side stream while the overlapped value
             # step runs there)
@@ -329,8 +339,11 @@ class DPPOWorker:
         if hasattr(self.engine, "raise_if_failed"):
             self.engine.raise_if_failed()        # (a timed-out per-step filter launch: never report it)
         v = st["host"].tolist()
-        kl_gate = None
-        if p.target_kl > 0:
+        kl_gate = lr_tail = None
+        if p.lr_schedule != "constant":
+            k = 3 if p.lr_schedule == "adaptive" else 1
+            lr_tail, v = v[-k:], v[:-k]
+        if p.gated():
             kl_gate, v = v[-4:], v[:-4]
         ret_std = v.pop() if p.reward_norm else None
         ep_ret, ep_cnt = v[0], v[1]
@@ -354,6 +367,11 @@ class DPPOWorker:
             m.update(kl_stopped=stopped, steps_applied=int(kl_gate[1]), kl_trip=kl_gate[2] if stopped else None,
                      updates=int(kl_gate[3]))
             self.updates = max(self.updates, int(kl_gate[3]))
+        if lr_tail is not None:
+            # lr_schedule: the rate the iteration ended with; adaptive: the cumulative decisions too
+            m["lr"] = lr_tail[0]
+            if len(lr_tail) == 3:
+                m.update(lr_downs=int(lr_tail[1]), lr_ups=int(lr_tail[2]))
         if p.verify_sync_every and st["iteration"] % p.verify_sync_every == 0:
             self.quiesce()                       # the checksum reads the value head too
             m["replicas_in_sync"] = self.ctx.verify_replicas(self.model.flat.data)
@@ -456,7 +474,7 @@ class DPPOWorker:
     def trainer_state(self) -> Dict:
         self.flush_pending()
         eng = self.engine
-        if self.p.target_kl > 0:
+        if self.p.gated():
             self.updates = int(eng.adam_step)    # the applied count (GPU engine: read from the device)
         return {"adam_m": eng.adam_m.detach().cpu(), "adam_v": eng.adam_v.detach().cpu(),
                 "adam_step": eng.adam_step, "obs_stats": self.stats.state_dict(),
@@ -465,6 +483,8 @@ class DPPOWorker:
                 # reward_norm: the running (n, mean, M2) of the discounted return (the per-rank carry
                 # ret_acc travels with the env state)
                 **({"ret_stats": eng.ret_stats.state_dict()} if self.p.reward_norm else {}),
+                # lr_schedule=adaptive: [lr, downs, ups, reserved] (linear's rate is a function of `iteration`)
+                **({"lr_state": eng.lr_state_dict()} if self.p.lr_schedule == "adaptive" else {}),
                 # fp8 mode's e4m3 wgrad operands: the gradient-maxima ring the next step's delayed
                 # scales come from (a resumed run continues bit-identically)
                 **({"q8_amax": eng.q8_amax.detach().cpu(), "q8_next": eng._q8_next}
@@ -485,6 +505,12 @@ class DPPOWorker:
                 eng.ret_stats.load_state_dict(st["ret_stats"])
             else:
                 warnings.warn("reward_norm: the checkpoint has no return statistics; they start empty", UserWarning,
+                              stacklevel=2)
+        if self.p.lr_schedule == "adaptive":
+            if "lr_state" in st:
+                eng.load_lr_state(st["lr_state"])
+            else:
+                warnings.warn("lr_schedule=adaptive: the checkpoint has no lr_state; the rate starts at lr", UserWarning,
                               stacklevel=2)
         if getattr(eng, "q8", False) and "q8_amax" in st:
             eng.q8_amax.copy_(st["q8_amax"].to(eng.q8_amax.device))
