@@ -528,12 +528,13 @@ int64_t train_lds_bytes(int64_t dt, std::vector<int64_t> layout, int64_t A) {
 // operand buffers' storage type and the parsed layout; the rest of this list leads its own.  tbufs: xT h1pT h2pT
 // h1vT h2vT g1pT g2pT g3pT g1vT g2vT g3vT, rows of ldT elements; idx empty: rows row0 .. row0 + M of x_buf; loss:
 // loss_kind (0 ppo, 1 dppo_ref), value_loss (0 mse, 1 clipped_half), std_var, first_step, clip, ent_coeff; part:
-// [ceil(M / ROWS)][npart] per-workgroup partial rows; xT_ready: xT holds the rows already.
+// [ceil(M / ROWS)][npart] per-workgroup partial rows; xT_ready: xT holds the rows already; adv_norm: the fp32
+// [mean, inv, std, explained variance] block of csrc/advnorm.hip that the policy loss normalises adv by (empty: off).
 using Tensors = const std::vector<torch::Tensor>&;
 MlpArgs train_args(int ROWS, int64_t nw, at::ScalarType operand, const Layout& L, int64_t dt, int64_t A, Tensors tbufs,
                    CT x_buf, CT idx, int64_t row0, int64_t M, CT wimg, const std::vector<double>& scales, CT flat,
                    CT log_std_old, CT actions, CT logp_old, CT adv, CT ret, CT v_old, CT mu_prev, CT v_prev,
-                   const std::vector<double>& loss, int64_t ldT, CT part, int64_t npart, bool xT_ready) {
+                   const std::vector<double>& loss, int64_t ldT, CT part, int64_t npart, bool xT_ready, CT adv_norm) {
   TORCH_CHECK(dt != 2, "the fp8 mode's update runs in bf16 (its e4m3 parts: the value fc1 image w8 and the wgrad operands q8_amax)");
   TORCH_CHECK(A > 0, "A");
   check(actions, "actions", at::kFloat, A);
@@ -568,6 +569,7 @@ MlpArgs train_args(int ROWS, int64_t nw, at::ScalarType operand, const Layout& L
   // a precomputed xT is only valid for the identity row order from row 0
   TORCH_CHECK(!xT_ready || (a.idx == nullptr && row0 == 0), "xT_ready needs a full-batch call");
   a.xT_ready = xT_ready ? 1 : 0;
+  if (adv_norm.defined() && adv_norm.numel() > 0) a.adv_norm = fptr(adv_norm, "adv_norm", 4);
   if (g_tstamp != nullptr) {
     TORCH_CHECK(g_tstamp_numel >= ((nblk + g_tstamp_every - 1) / g_tstamp_every) * nw * 16, "tstamp buffer too small");
     a.tstamp = g_tstamp;
@@ -951,6 +953,45 @@ void ret_scan(torch::Tensor rewards, torch::Tensor dones, torch::Tensor ret_acc,
   after_launch(__func__);
 }
 
+// adv_norm_scope global | minibatch (csrc/advnorm.hip): sums fp64[4] = [sum a, sum a^2, sum r, sum r^2] over the n rows
+// idx ? idx[i] : i of adv / ret (idx empty: the first n rows; ret empty: its two sums are 0), in a fixed order; part:
+// fp64 scratch of adv_stats_nblk(n) x 4; block (empty: the sums only): fp32[4] = [mean, inv, std, explained variance]
+// finished from the sums with the count n_total in the same two launches.  adv_block: the finish alone, for sums that
+// were all-reduced in between.  The indices are the caller's to range-check (the kernel clamps them to the buffer).
+int64_t adv_stats_nblk(int64_t n) {
+  TORCH_CHECK(n >= 1 && n < (int64_t(1) << 31), "adv_stats: n");
+  return adv_stats_blocks((int)n);
+}
+
+void adv_stats(torch::Tensor adv, torch::Tensor ret, torch::Tensor idx, int64_t n, torch::Tensor part, torch::Tensor sums,
+               double n_total, torch::Tensor block) {
+  TORCH_CHECK(n >= 2 && n < (int64_t(1) << 31), "adv_stats: n >= 2 rows (the unbiased variance), got ", n);
+  TORCH_CHECK(n_total >= 2.0, "adv_stats: n_total >= 2, got ", n_total);
+  const bool has_idx = idx.defined() && idx.numel() > 0, has_ret = ret.defined() && ret.numel() > 0;
+  check(adv, "adv", at::kFloat, has_idx ? 1 : n);
+  TORCH_CHECK(adv.numel() < (int64_t(1) << 31), "adv_stats: 32-bit row indices");
+  if (has_idx) check(idx, "idx", at::kInt, n);
+  if (has_ret) {
+    check(ret, "ret", at::kFloat, adv.numel());
+    TORCH_CHECK(ret.numel() == adv.numel(), "adv_stats: ret must have adv's ", adv.numel(), " rows, got ", ret.numel());
+  }
+  check(part, "part", at::kDouble, 4 * adv_stats_nblk(n));
+  check(sums, "sums", at::kDouble, 4);
+  float* b = nullptr;
+  if (block.defined() && block.numel() > 0) b = fptr(block, "block", 4);
+  launch_adv_stats(adv.data_ptr<float>(), has_ret ? ret.data_ptr<float>() : nullptr,
+                   has_idx ? idx.data_ptr<int>() : nullptr, (int)n, (int)adv.numel(), part.data_ptr<double>(),
+                   sums.data_ptr<double>(), n_total, b, cur_stream());
+  after_launch(__func__);
+}
+
+void adv_block(torch::Tensor sums, double n_total, torch::Tensor block) {
+  TORCH_CHECK(n_total >= 2.0, "adv_block: n_total >= 2, got ", n_total);
+  check(sums, "sums", at::kDouble, 4);
+  launch_adv_block(sums.data_ptr<double>(), n_total, fptr(block, "block", 4), cur_stream());
+  after_launch(__func__);
+}
+
 void metrics_pack(torch::Tensor ep, torch::Tensor loss8, torch::Tensor norm_part, torch::Tensor out) {
   check(ep, "ep", at::kDouble, 2);
   check(loss8, "loss8", at::kFloat, 8);
@@ -1194,6 +1235,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gae_rn", &gae_rn);
   m.def("ret_scan", &ret_scan);
   m.def("ret_scan_nblk", &ret_scan_nblk);
+  m.def("adv_stats", &adv_stats);
+  m.def("adv_block", &adv_block);
+  m.def("adv_stats_nblk", &adv_stats_nblk);
   m.def("set_adam_fused", [](int64_t on) { set_adam_fused((int)on); });
   m.def("obs_reduce", &obs_reduce);
   m.def("obs_merge", &obs_merge);

@@ -20,6 +20,13 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 #define DEV __device__ __forceinline__
+// MlpArgs::adv_norm at the update kernels' advantage load: a' = fl32(fl32(a - mean) * inv), two separately
+// rounded fp32 operations (ops/oracle.adv_apply); the product carries no contract flag, so no later add fuses it
+DEV float adv_norm_apply(float a, float mean, float inv) {
+#pragma clang fp contract(off)
+  const float d = a - mean;
+  return d * inv;
+}
 typedef __attribute__((ext_vector_type(8))) float f32x8v;
 // Elementwise fp32 vector arithmetic of the MFMA epilogues / operand splits (packed v_pk_* f32 ops;
 // scalar spellings measured mixed in round 4, profiles/r4/ab_nopk/)

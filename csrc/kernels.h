@@ -219,6 +219,11 @@ struct MlpArgs {
   // stamps at the phase boundaries of every tstamp_every-th workgroup, [blk][NW][16]
   unsigned long long* tstamp;
   int tstamp_every;
+  // (last: every earlier member keeps its kernel-argument offset)
+  // adv_norm_scope global | minibatch: [mean, inv, ..] fp32 on the device (csrc/advnorm.hip); the policy loss
+  // reads a' = fl32(fl32(adv - mean) * inv) (common.h adv_norm_apply), adv itself stays raw.  null: off.
+  // The value head and the forward mode ignore it.
+  const float* adv_norm;
 };
 
 // per-head streaming update (csrc/mlp_head.hip): head 0 = policy, 1 = value; 128 rows per workgroup
@@ -386,6 +391,14 @@ void launch_gae_rn(const float* rewards, const float* values, const float* dones
 int ret_scan_blocks(int T, int E, int mode);
 void launch_ret_scan(const float* rewards, const float* dones, float* acc, const float* shift, float* R_out,
                      double* part, double* s12, int T, int E, float gamma, int mode, hipStream_t s);
+// csrc/advnorm.hip: sums fp64[4] = [sum a, sum a^2, sum r, sum r^2] over rows idx ? idx[i] : i, i < n, of adv / ret
+// [nrows] (ret null: its sums are 0; idx null: n <= nrows), in a fixed order; part: adv_stats_blocks(n) x 4 doubles
+// of scratch; block (optional) fp32[4] = [mean, inv, std, explained variance] finished from the sums with the count
+// n_total in the same two launches.  launch_adv_block: the finish alone (an all-reduce of the sums in between).
+int adv_stats_blocks(int n);
+void launch_adv_stats(const float* adv, const float* ret, const int* idx, int n, int nrows, double* part, double* sums,
+                      double n_total, float* block, hipStream_t s);
+void launch_adv_block(const double* sums, double n_total, float* block, hipStream_t s);
 void set_adam_fused(int on);
 // one launch without clipping when the step number is known (host_step > 0 or gated), else sumsq + adam
 void launch_adam(const AdamArgs& a, hipStream_t s);

@@ -221,6 +221,15 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
   const int m0 = blockIdx.x * ROWS;
   const int nvalid = min(ROWS, a.M - m0);
   const int A = a.A;
+  // adv_norm (csrc/advnorm.hip's block): its two operands, loaded and settled here, ahead of every other memory
+  // operation of the kernel (the asm redefines the registers: scalar registers for the whole kernel, and no load
+  // of theirs in flight among the weight prefetches' counted waits); applied where the loss reads the advantage
+  float an_m = 0.f, an_s = 1.f;
+  if (a.adv_norm != nullptr) {
+    an_m = a.adv_norm[0];
+    an_s = a.adv_norm[1];
+    asm volatile("" : "+s"(an_m), "+s"(an_s));
+  }
   const int ldx = Lds<DT>::stride(a.d_in[0]);
   const int ld1p = Lds<DT>::stride(a.d_in[1]);
   const int ld2p = Lds<DT>::stride(a.d_in[2]);
@@ -362,7 +371,7 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
         if (q == u) x = actv[u];
       return x;
     };
-    const float advv = l_adv;
+    const float advv = a.adv_norm != nullptr ? adv_norm_apply(l_adv, an_m, an_s) : l_adv;
     const float v = V[r];
     const float cvar = a.std_var ? 0.5f : 1.f;
     float lclip = 0.f, lent = 0.f, kl = 0.f, cf = 0.f, vold;

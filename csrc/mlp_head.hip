@@ -503,6 +503,18 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
     l_vold = !ref_loss ? a.v_old[lsrc] : 0.f;
     l_vprev = ref_loss ? a.v_prev[lsrc] : 0.f;
   }
+  // adv_norm (csrc/advnorm.hip's block; the policy head's update only): its two operands are loaded beside the
+  // loss inputs and applied where the loss reads l_adv.  They are scalar loads, counted on lgkmcnt with the
+  // stream's LDS reads: the asm redefines the registers, so the compiler settles them here, before the first DMA,
+  // and carries no pending scalar load into the counted stream (where it would turn counted waits into full ones)
+  float an_m = 0.f, an_s = 1.f;
+  if constexpr (HEAD == 0) {
+    if (a.adv_norm != nullptr) {
+      an_m = a.adv_norm[0];
+      an_s = a.adv_norm[1];
+      asm volatile("" : "+s"(an_m), "+s"(an_s));
+    }
+  }
 
   // ---- DMA sources ----
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), (short)0, 0x7fffffff, 0x00020000);
@@ -1032,6 +1044,7 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
     const bool valid = lvalid;
     const float cvar = a.std_var ? 0.5f : 1.f;
     float lclip = 0.f, lent = 0.f, kl = 0.f, cf = 0.f;
+    if (a.adv_norm != nullptr) l_adv = adv_norm_apply(l_adv, an_m, an_s);
     if (a.loss_kind == 0) {
       // ---- corrected PPO (ppo.py:148-167) ----
       float logp = 0.f;

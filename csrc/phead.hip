@@ -122,6 +122,12 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
   }
   float l_adv = a.adv[srow];
   float l_lpo = ref_loss ? 0.f : a.logp_old[srow];
+  // adv_norm (csrc/advnorm.hip's block): its two operands, loaded here with the loss inputs
+  float an_m = 0.f, an_s = 1.f;
+  if (a.adv_norm != nullptr) {
+    an_m = a.adv_norm[0];
+    an_s = a.adv_norm[1];
+  }
   if (tid < 64) {
     const int j = tid & 31;
     lsd[tid] = tid < 32 ? (j < A ? a.log_std[j] : 0.f) : ((ref_loss && j < A) ? a.log_std_old[j] : 0.f);
@@ -211,6 +217,10 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
   // registers, so no compiler-inserted wait for them falls inside the counted stream (where it
   // would also wait for every in-flight DMA and operand store)
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(l_adv), "+v"(l_lpo)::"memory");
+  // ... and the advantage is normalised here, its operands landed by the same wait: the second asm keeps the
+  // arithmetic (and with it the operands' registers) from sinking into the stream
+  if (a.adv_norm != nullptr) l_adv = adv_norm_apply(l_adv, an_m, an_s);
+  asm volatile("" : "+v"(l_adv));
   // ---- prime: X stages 0, 1 and ring stages 0, 1 (the launcher checks ns1 >= 3) ----
   static_assert(PH_S == 3 && PH_XS == 3, "the wait counts below are written for 3-stage rings");
   issue_x(0);

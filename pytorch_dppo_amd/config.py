@@ -70,6 +70,13 @@ class Params:
     obs_norm_update: str = "rollout"     # step (model.py:68 per step) | rollout (one merge per rollout)
     reward_clip: float = 1.0             # train.py:96 clips to +-1; <=0 disables
     normalize_adv: bool = False
+    adv_norm_scope: str = "rank"         # read with normalize_adv only.  rank: each rank normalises its own T*E
+                                         # advantages in place (torch ops) | global: one mean / std over the T*E*W
+                                         # advantages of all W ranks | minibatch: over this rank's rows of the current
+                                         # update step, recomputed before every step, no collective (the CleanRL /
+                                         # Stable-Baselines3 rule).  global and minibatch leave adv raw — the update
+                                         # kernels apply the statistics at their advantage load (csrc/advnorm.hip,
+                                         # ops/oracle.adv_block) — and log adv_mean, adv_std and explained_variance.
     bootstrap_time_limit: bool = False   # an episode ended by the step limit alone (truncated, not terminal) is
                                          # bootstrapped with V of the observation the env reached before its reset:
                                          # delta_t = r_t + gamma * V(s_{t+1}^true) - V_t, recursion still cut.  False: the
@@ -222,6 +229,18 @@ class Params:
             if self.stats_stream != "off":
                 raise ValueError("reward_norm is not built for stats_stream=on|auto: the return scale is merged on "
                                  "the compute stream before GAE reads it; use stats_stream=off")
+        if self.adv_norm_scope not in ("rank", "global", "minibatch"):
+            raise ValueError(f"adv_norm_scope must be rank|global|minibatch, got {self.adv_norm_scope}")
+        if self.adv_norm_scope != "rank":
+            if not self.normalize_adv:
+                raise ValueError(f"adv_norm_scope={self.adv_norm_scope} is a scope of normalize_adv: set normalize_adv "
+                                 "true")
+            if self.adv_norm_scope == "minibatch" and self.minibatch_rows() < 2:
+                raise ValueError("adv_norm_scope=minibatch needs a minibatch of at least 2 rows (the unbiased std), got "
+                                 f"{self.minibatch_rows()}")
+            if self.adv_norm_scope == "global" and self.buffer_rows * self.num_processes < 2:
+                raise ValueError("adv_norm_scope=global needs at least 2 advantages per iteration (the unbiased std), "
+                                 f"got {self.buffer_rows * self.num_processes}")
 
         self.target_kl = float(self.target_kl)
         if not self.target_kl >= 0:
@@ -266,6 +285,11 @@ class Params:
                 raise ValueError("lr_schedule=adaptive cannot be combined with overlap_rollout / overlap_value_epochs: "
                                  "they move a value step to a side stream or behind the next rollout, and an adaptive "
                                  "step reads the device rate and counter in stream order")
+
+    def adv_scope(self) -> str:
+        """the advantage normalisation applied at the loss: "global" | "minibatch", or "" (off, and scope rank, which
+        normalises the buffer in place)"""
+        return self.adv_norm_scope if (self.normalize_adv and self.adv_norm_scope != "rank") else ""
 
     def gated(self) -> bool:
         """the update steps run through the KL gate (target_kl, or the adaptive rate, which lives behind it)"""

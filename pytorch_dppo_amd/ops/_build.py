@@ -25,7 +25,7 @@ EXT_NAME = "_dppo_hip"
 ARCH = os.environ.get("DPPO_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 DEVICE_SRCS = ["rollout.hip", "eval.hip", "act.hip", "envstep.hip", "mlp.hip", "mlp_head.hip", "phead.hip", "wgrad.hip", "optim.hip", "obs.hip",
-               "retnorm.hip"]
+               "retnorm.hip", "advnorm.hip"]
 HOST_SRCS = ["bindings.cpp", "comm.cpp"]   # compiled with the torch include paths
 
 

@@ -265,6 +265,45 @@ def lr_adapt_dir(kl, kl_target: float) -> int:
     return -1 if bool(kl > f32(2.0) * t) else (1 if bool(kl < f32(0.5) * t) else 0)
 
 
+def adv_sums(adv: torch.Tensor, ret: torch.Tensor, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``adv_norm_scope`` global | minibatch: fp64 ``[sum a, sum a^2, sum r, sum r^2]`` over the rows of ``adv`` /
+    ``ret`` (the twin of ``csrc/advnorm.hip`` adv_stats_kernel + adv_moments_kernel; the kernels' order of summation
+    differs, within fp64 rounding).  With ``idx`` the rows are gathered first, so a duplicated row counts twice."""
+    a = adv.reshape(-1).to(torch.float64)
+    r = ret.reshape(-1).to(torch.float64)
+    if idx is not None:
+        i = idx.reshape(-1).to(torch.int64)
+        a, r = a[i], r[i]
+    return torch.stack([a.sum(), (a * a).sum(), r.sum(), (r * r).sum()])
+
+
+def adv_block(sums: torch.Tensor, n) -> torch.Tensor:
+    """fp32 ``[mean, inv, std, explained_variance]`` of ``n`` advantages (and returns) from their ``adv_sums`` (the
+    twin of ``csrc/advnorm.hip`` adv_finish), in fp64 with every operation rounded on its own, rounded to fp32 once::
+
+        mean = S1 / n;  var = max(S2 - S1 * mean, 0) / (n - 1);  std = sqrt(var);  inv = 1 / (std + 1e-8)
+        explained_variance = 1 - var / var_ret      (var_ret likewise from S3, S4; NaN when var_ret = 0)
+
+    The variance is the unbiased estimator, as ``torch.std`` uses under scope ``rank``."""
+    S1, S2, R1, R2 = (float(x) for x in sums.to(torch.float64).reshape(-1).tolist())
+    n = float(n)
+    mean = S1 / n
+    var = max(S2 - S1 * mean, 0.0) / (n - 1.0)
+    std = math.sqrt(var)
+    inv = 1.0 / (std + 1e-8)
+    rmean = R1 / n
+    rvar = max(R2 - R1 * rmean, 0.0) / (n - 1.0)
+    ev = 1.0 - var / rvar if rvar > 0.0 else float("nan")
+    return torch.tensor([mean, inv, std, ev], dtype=torch.float64).to(torch.float32)
+
+
+def adv_apply(adv: torch.Tensor, block: torch.Tensor) -> torch.Tensor:
+    """the advantage the loss reads under ``adv_norm_scope`` global | minibatch: ``(adv - mean) * inv`` as two
+    separately rounded fp32 operations (csrc/common.h adv_norm_apply); ``adv`` itself is left raw"""
+    b = block.to(device=adv.device, dtype=torch.float32)
+    return (adv.to(torch.float32) - b[0]) * b[1]
+
+
 def adam_step_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,
                lr: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
     """torch.optim.Adam (default, non-amsgrad, no weight decay) on flat buffers."""

@@ -429,6 +429,22 @@ class HipEngine:
         n_lr = {"constant": 0, "linear": 1, "adaptive": 3}[params.lr_schedule]
         if self.gate is not None or n_lr:
             self.metrics_buf = torch.zeros(self._m_lr + n_lr, dtype=torch.float64, **dev)
+        # adv_norm_scope global | minibatch (docs/ARCHITECTURE.md §24): adv stays raw and the policy kernels apply
+        # [mean, inv] at their advantage load.  adv_blocks = [the whole buffer's block (global: every rank's) | the
+        # current step's (minibatch)], each fp32 [mean, inv, std, explained variance], written by csrc/advnorm.hip
+        # on the compute stream; _adv_arg is the one the next update launch reads (_minibatch picks it; empty: off);
+        # three more slots of the metrics vector.  Allocated only with the flag on.
+        self.adv_scope = params.adv_scope()
+        self.adv_block: Optional[torch.Tensor] = None
+        self._adv_arg = self.no_q
+        self._m_adv = self._m_lr + n_lr
+        if self.adv_scope:
+            self.adv_blocks = torch.zeros(2, 4, **f32)
+            self.adv_block, self.adv_block_mb = self.adv_blocks[0], self.adv_blocks[1]
+            self._adv_arg = self.adv_block
+            self.adv_sums_buf = torch.zeros(2, 4, dtype=torch.float64, **dev)     # likewise [buffer | step]
+            self.adv_part = torch.zeros(4 * int(self.ext.adv_stats_nblk(self.N)), dtype=torch.float64, **dev)
+            self.metrics_buf = torch.zeros(self._m_adv + 3, dtype=torch.float64, **dev)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -1294,9 +1310,26 @@ class HipEngine:
             self.ext.gae(self.rewards.view(T, E), self.values_buf.view(T + 1, E), self.dones.view(T, E),
                          self.adv.view(T, E), self.ret.view(T, E), float(self.p.gamma), float(self.p.gae_param), 0,
                          self.p.gae_segment())
-        if self.p.normalize_adv:
+        if self.p.normalize_adv and not self.adv_scope:
             m, s = self.adv.mean(), self.adv.std()
             self.adv.sub_(m).div_(s + 1e-8)
+
+    @torch.no_grad()
+    def adv_sums(self, finish: bool = True) -> torch.Tensor:
+        """adv_norm_scope global | minibatch, after gae(): device fp64 [sum a, sum a^2, sum r, sum r^2] of this
+        rank's whole buffer (csrc/advnorm.hip: two launches, no host sync).  ``finish``: they are the iteration's
+        (no other rank's join them) and the second launch also writes ``adv_block``; else the worker sums them over
+        the ranks in stream order and hands them to ``set_adv_sums`` (one more launch)."""
+        self.ext.adv_stats(self.adv, self.ret, self.empty, self.N, self.adv_part, self.adv_sums_buf[0], float(self.N),
+                           self.adv_block if finish else self.no_q)
+        return self.adv_sums_buf[0]
+
+    def set_adv_sums(self, sums: torch.Tensor, n: float) -> None:
+        self.ext.adv_block(sums, float(n), self.adv_block)
+
+    def adv_tail(self) -> torch.Tensor:
+        """the metrics vector's [adv_mean, adv_std, explained_variance] where pack_metrics does not run"""
+        return torch.cat([self.adv_block[0:1], self.adv_block[2:4]])
 
     def _keep_log_std(self) -> None:
         """train.py:164: log_std as this step's kernels read it, kept for the next step before Adam moves it (only the
@@ -1332,6 +1365,14 @@ class HipEngine:
                 raise IndexError(f"minibatch indices out of range [0, {self.N}): {lo}..{hi}")
             self.idx_dev[:M].copy_(idx.to(torch.int32), non_blocking=True)
             idx_t = self.idx_dev
+        if self.adv_scope:
+            # minibatch scope: the block of this step's own rows (duplicates counted), two launches ahead of the
+            # step's kernels; a full-batch step reads the whole buffer's block
+            self._adv_arg = self.adv_block
+            if self.adv_scope == "minibatch" and idx is not None:
+                self.ext.adv_stats(self.adv, self.no_q, self.idx_dev, M, self.adv_part, self.adv_sums_buf[1], float(M),
+                                   self.adv_block_mb)
+                self._adv_arg = self.adv_block_mb
         first, xt_ready = bool(self._first_step), bool(idx is None and self._xT_valid)
         xmode = "fm"
         if self.phead:
@@ -1514,13 +1555,14 @@ class HipEngine:
         """the positional block that leads ext.mlp_train, ext.mlp_head_train and ext.phead_train (csrc/bindings.cpp
         train_args): dt, A, the 11 operand buffers, the layout; x_buf, idx, row0, M; the weight image, scales, flat,
         log_std_old; actions, logp, adv, ret, values and mu_prev / v_prev; loss = [loss_kind, value_loss, std_var,
-        first_step, clip, ent_coeff]; ldT; the partial rows and their width; xt_ready"""
+        first_step, clip, ent_coeff]; ldT; the partial rows and their width; xt_ready; the advantage block of
+        adv_norm_scope global | minibatch (empty: off)"""
         p = self.p
         loss = [float(p.loss != "ppo"), float(p.value_loss != "mse"), float(self.std_var), float(first),
                 float(p.clip), float(p.ent_coeff)]
         return (self.dt, self.A, self.tbufs, self.layout, self.x_buf, idx_t, 0, self.mb, self.wimg, self.scales,
                 self.model.flat.data, self.log_std_old, self.actions, self.logp, self.adv, self.ret, self.values_buf,
-                self.mu_prev, self.v_prev, loss, self.ldT, part, part.shape[1], xt_ready)
+                self.mu_prev, self.v_prev, loss, self.ldT, part, part.shape[1], xt_ready, self._adv_arg)
 
     def _head_kernel(self, h: int, idx_t, first: bool, xt_ready: bool, part: torch.Tensor, part_dw: int) -> None:
         args = self._update_args(idx_t, first, xt_ready, part)
@@ -1693,8 +1735,12 @@ class HipEngine:
                 self.metrics_buf[g0 + 3:g0 + 4].copy_(self.adam_state[0:1])
             if self.lr_state is not None:       # [lr, downs, ups] behind the gate tail
                 self.metrics_buf[self._m_lr:self._m_lr + 3].copy_(self.lr_state[:3])
-            elif self.metrics_buf.numel() > self._m_lr:     # linear: the iteration's host rate
-                self.metrics_buf[self._m_lr:].fill_(self.lr)
+            elif self._m_adv > self._m_lr:                  # linear: the iteration's host rate
+                self.metrics_buf[self._m_lr:self._m_adv].fill_(self.lr)
+            if self.adv_scope:                  # [adv_mean, adv_std, explained_variance] behind the lr tail
+                a0 = self._m_adv
+                self.metrics_buf[a0:a0 + 1].copy_(self.adv_block[0:1])
+                self.metrics_buf[a0 + 1:a0 + 3].copy_(self.adv_block[2:4])
         return self.metrics_buf
 
     def lr_tail(self) -> torch.Tensor:

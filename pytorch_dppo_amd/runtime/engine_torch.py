@@ -83,6 +83,11 @@ class TorchEngine:
         if params.lr_schedule == "adaptive":
             self.lr = float(torch.tensor(params.lr, dtype=torch.float32))
             self.lr_state = [self.lr, 0.0, 0.0, 0.0]
+        # adv_norm_scope global | minibatch: adv stays raw; adv_block = fp32 [mean, inv, std, explained variance] of
+        # the whole buffer (global: of every rank's), set after gae() through adv_sums() / set_adv_sums(); grad()
+        # applies it to the gathered rows (minibatch: the block of the step's own rows).  Only with the flag on.
+        self.adv_scope = params.adv_scope()
+        self.adv_block: Optional[torch.Tensor] = None
         self.flat_old = model.flat.detach().clone()  # dppo_ref "model_old" (train.py:128-129,164)
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.obs = env.reset().to(device)
@@ -178,10 +183,27 @@ class TorchEngine:
             rewards = oracle.scale_rewards(rewards, self.ret_stats.scale, float(self.p.reward_norm_clip))
         adv, ret = oracle.gae(rewards, self.values_buf, self.dones, self.p.gamma, self.p.gae_param,
                               segment=self.p.gae_segment(), boot=boot)
-        if self.p.normalize_adv:
+        if self.p.normalize_adv and not self.adv_scope:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         self.adv.copy_(adv)
         self.ret.copy_(ret)
+
+    @torch.no_grad()
+    def adv_sums(self, finish: bool = True) -> torch.Tensor:
+        """adv_norm_scope global | minibatch, after gae(): fp64 [sum a, sum a^2, sum r, sum r^2] of this rank's whole
+        buffer (ops/oracle.adv_sums).  ``finish``: they are the iteration's (no other rank's join them) and become
+        the block here; else the worker sums them over the ranks and hands them to ``set_adv_sums``."""
+        sums = oracle.adv_sums(self.adv, self.ret)
+        if finish:
+            self.set_adv_sums(sums, float(self.T * self.E))
+        return sums
+
+    def set_adv_sums(self, sums: torch.Tensor, n: float) -> None:
+        self.adv_block = oracle.adv_block(sums, n)
+
+    def adv_tail(self) -> torch.Tensor:
+        """the metrics vector's [adv_mean, adv_std, explained_variance] of the raw whole-buffer advantages"""
+        return self.adv_block[[0, 2, 3]].to(torch.float64)
 
     def current_obs(self) -> torch.Tensor:
         return self.obs
@@ -219,12 +241,18 @@ class TorchEngine:
         """loss + backward on rows ``idx`` of the flattened [T*E] buffer -> self.grad_flat."""
         p = self.p
         N = self.T * self.E
-        if idx is None:
+        full = idx is None
+        if full:
             idx = torch.arange(N, device=self.device)
         x = self.x[:self.T].reshape(N, self.O)[idx]
         a = self.actions.reshape(N, self.A)[idx]
         adv = self.adv.reshape(N)[idx]
         ret = self.ret.reshape(N)[idx]
+        if self.adv_scope:
+            block = self.adv_block
+            if self.adv_scope == "minibatch" and not full:
+                block = oracle.adv_block(oracle.adv_sums(self.adv, self.ret, idx), idx.numel())
+            adv = oracle.adv_apply(adv, block)
         self.model.flat.grad = None
         mu, log_std, v = self.model(x)
         if p.loss == "ppo":

@@ -182,6 +182,14 @@ class DPPOWorker:
         tm.start("values_gae")
         eng.values()
         eng.gae()
+        if p.adv_scope():
+            # adv_norm_scope global | minibatch: the whole buffer's sums become the engine's block (the loss reads
+            # it under global and at a full-batch step; the record's adv_mean / adv_std / explained_variance);
+            # global over several ranks: summed in stream order first, with the host-known count (no host read)
+            reduce = p.adv_scope() == "global" and self.ctx.collective
+            sums = eng.adv_sums(finish=not reduce)
+            if reduce:
+                eng.set_adv_sums(self.ctx.allreduce_tensor_(sums), float(eng.T * eng.E * self.ctx.world_size))
         tm.stop("values_gae")
         tm.start("update")
         if p.lr_schedule == "linear":
@@ -305,6 +313,8 @@ class DPPOWorker:
                 flat = torch.cat([flat, tail.to(flat.device, torch.float64)])
             if self.p.lr_schedule != "constant":   # [lr, downs, ups] (adaptive) or [lr] (linear), behind the gate tail
                 flat = torch.cat([flat, eng.lr_tail().to(flat.device, torch.float64)])
+            if self.p.adv_scope():     # [adv_mean, adv_std, explained_variance], behind the lr tail
+                flat = torch.cat([flat, eng.adv_tail().to(flat.device, torch.float64)])
         if dev.type == "cuda":
             # the stream the metrics were packed on (the side stream while the overlapped value
             # step runs there)
@@ -339,7 +349,9 @@ class DPPOWorker:
         if hasattr(self.engine, "raise_if_failed"):
             self.engine.raise_if_failed()        # (a timed-out per-step filter launch: never report it)
         v = st["host"].tolist()
-        kl_gate = lr_tail = None
+        kl_gate = lr_tail = adv_tail = None
+        if p.adv_scope():
+            adv_tail, v = v[-3:], v[:-3]
         if p.lr_schedule != "constant":
             k = 3 if p.lr_schedule == "adaptive" else 1
             lr_tail, v = v[-k:], v[:-k]
@@ -372,6 +384,11 @@ class DPPOWorker:
             m["lr"] = lr_tail[0]
             if len(lr_tail) == 3:
                 m.update(lr_downs=int(lr_tail[1]), lr_ups=int(lr_tail[2]))
+        if adv_tail is not None:
+            # adv_norm_scope global | minibatch: of the raw advantages of the whole buffer (global: every rank's);
+            # explained_variance = 1 - var(adv) / var(ret) is undefined (null) for a constant return
+            m.update(adv_mean=adv_tail[0], adv_std=adv_tail[1],
+                     explained_variance=None if math.isnan(adv_tail[2]) else adv_tail[2])
         if p.verify_sync_every and st["iteration"] % p.verify_sync_every == 0:
             self.quiesce()                       # the checksum reads the value head too
             m["replicas_in_sync"] = self.ctx.verify_replicas(self.model.flat.data)
