@@ -33,10 +33,11 @@ from ..ops import native, storage
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
 from ..utils.ret_stats import VAR_FLOOR as RET_VAR_FLOOR, RunningReturnStats
+from .engine import Engine
 from .engine_torch import load_ret_acc
+from .metrics_layout import NPART_FIXED, MetricsLayout
 
 STORAGE = storage.STORAGE
-NPART_FIXED = 8
 Q8_SX, Q8_SH = 64.0, 256.0   # fixed e4m3 operand scales of the observations / tanh activations (csrc/common.h)
 Q8_SUB = 64                  # sub-slots per tensor of the gradient-amax ring (csrc/kernels.h)
 WT = 128            # operand-buffer row padding (csrc/kernels.h WGRAD_TILE)
@@ -87,8 +88,9 @@ def _r(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-class HipEngine:
+class HipEngine(Engine):
     name = "hip"
+    has_stats_stream = True
 
     def __init__(self, params: Params, model: ActorCritic, env, stats: RunningObsStats,
                  device: torch.device, action_rank: int):
@@ -360,7 +362,9 @@ class HipEngine:
         self._loss_dev: Optional[torch.Tensor] = None
         self.local_stats: Optional[RunningObsStats] = None
         self.loss_sums = torch.zeros(NPART_FIXED, **f32) if self.gate is None else self._grad_sums[n:]
-        self.metrics_buf = torch.zeros(2 + NPART_FIXED + 1, dtype=torch.float64, **dev)
+        # the iteration's metrics vector (pack_metrics), allocated once
+        self.metrics_layout = MetricsLayout(params)
+        self.metrics_buf = torch.zeros(self.metrics_layout.size, dtype=torch.float64, **dev)
         self.empty_x = torch.empty(0, dtype=self.sdtype, **dev)
         self.x_raw: Optional[torch.Tensor] = None   # compat Q8: raw bootstrap rows (values())
         # the rollout can emit the full-batch x^T operand when the update is one full-batch step
@@ -409,8 +413,7 @@ class HipEngine:
             self._fin_slot = None
         # reward_norm: the carry of the discounted-return scan (per rank, checkpointed with the env),
         # the running statistics of the return (global; merged by csrc/obs.hip obs_merge with O = 1),
-        # the scan's (S1, S2) and per-workgroup scratch (csrc/retnorm.hip), and one more slot of the
-        # metrics vector (return_std).  Allocated only with the flag on.
+        # the scan's (S1, S2) and per-workgroup scratch (csrc/retnorm.hip).  Allocated only with the flag on.
         self.ret_stats: Optional[RunningReturnStats] = None
         self.ret_acc: Optional[torch.Tensor] = None
         if bool(getattr(params, "reward_norm", False)):
@@ -419,32 +422,20 @@ class HipEngine:
             self.ret_acc = torch.zeros(E, **f32)
             self.ret_s12 = torch.zeros(2, dtype=torch.float64, **dev)
             self.ret_part = torch.zeros(2 * int(self.ext.ret_scan_nblk(T, E, 0)), dtype=torch.float64, **dev)
-            self.metrics_buf = torch.zeros(2 + NPART_FIXED + 2, dtype=torch.float64, **dev)
-        # the metrics vector's slots behind metrics_pack's 11: return_std (reward_norm), then
-        # [stop, applied, trip_kl, applied since the start of training] (target_kl)
-        self._m_ret = 2 + NPART_FIXED + 1
-        self._m_gate = self._m_ret + (1 if self.ret_stats is not None else 0)
-        # ... then lr_schedule's [lr, downs, ups] (adaptive) or [lr] (linear)
-        self._m_lr = self._m_gate + (4 if self.gate is not None else 0)
-        n_lr = {"constant": 0, "linear": 1, "adaptive": 3}[params.lr_schedule]
-        if self.gate is not None or n_lr:
-            self.metrics_buf = torch.zeros(self._m_lr + n_lr, dtype=torch.float64, **dev)
         # adv_norm_scope global | minibatch (docs/ARCHITECTURE.md §24): adv stays raw and the policy kernels apply
         # [mean, inv] at their advantage load.  adv_blocks = [the whole buffer's block (global: every rank's) | the
         # current step's (minibatch)], each fp32 [mean, inv, std, explained variance], written by csrc/advnorm.hip
-        # on the compute stream; _adv_arg is the one the next update launch reads (_minibatch picks it; empty: off);
-        # three more slots of the metrics vector.  Allocated only with the flag on.
+        # on the compute stream; _adv_arg is the one the next update launch reads (_minibatch picks it; empty: off).
+        # Allocated only with the flag on.
         self.adv_scope = params.adv_scope()
         self.adv_block: Optional[torch.Tensor] = None
         self._adv_arg = self.no_q
-        self._m_adv = self._m_lr + n_lr
         if self.adv_scope:
             self.adv_blocks = torch.zeros(2, 4, **f32)
             self.adv_block, self.adv_block_mb = self.adv_blocks[0], self.adv_blocks[1]
             self._adv_arg = self.adv_block
             self.adv_sums_buf = torch.zeros(2, 4, dtype=torch.float64, **dev)     # likewise [buffer | step]
             self.adv_part = torch.zeros(4 * int(self.ext.adv_stats_nblk(self.N)), dtype=torch.float64, **dev)
-            self.metrics_buf = torch.zeros(self._m_adv + 3, dtype=torch.float64, **dev)
         obs0 = env.reset()
         self._host_obs = obs0.to(device) if self.host_env else None
         self.params_changed()
@@ -1327,10 +1318,6 @@ class HipEngine:
     def set_adv_sums(self, sums: torch.Tensor, n: float) -> None:
         self.ext.adv_block(sums, float(n), self.adv_block)
 
-    def adv_tail(self) -> torch.Tensor:
-        """the metrics vector's [adv_mean, adv_std, explained_variance] where pack_metrics does not run"""
-        return torch.cat([self.adv_block[0:1], self.adv_block[2:4]])
-
     def _keep_log_std(self) -> None:
         """train.py:164: log_std as this step's kernels read it, kept for the next step before Adam moves it (only the
         reference loss reads it)"""
@@ -1398,9 +1385,10 @@ class HipEngine:
                 and (self.heads or (len(self.buckets) == 1 and self.buckets[0]["partials"])))
 
     def step(self, idx: Optional[torch.Tensor], extra_grad: float = 0.0, allreduce=None,
-             mean: bool = False, last: bool = False) -> None:
+             mean: bool = False, last: bool = False) -> bool:
         """ONE synchronous global step (train.py:133-175 + chief.py:13-20): the minibatch
-        gradient, its sum (``mean``: average) over ranks, and the Adam step.
+        gradient, its sum (``mean``: average) over ranks, and the Adam step.  True: the host counts
+        one applied update (gated: the device counts them, adam_state[0]).
 
         ``allreduce``: the worker's collective (parallel/dist.py grad_allreduce_fn), None at world
         size 1.  In-stream communicators (``allreduce.in_stream``: the native RCCL one — the
@@ -1420,10 +1408,14 @@ class HipEngine:
         that head's kernel of step e+1, so the parameters are exactly the synchronous ones.
         Clipping (a global norm over both heads), the Q1 extra gradient and the one-kernel tile
         update take the whole-vector path."""
-        p = self.p
         if self.gate is not None:
             self._gated_step(idx, extra_grad, allreduce, mean)
-            return
+            return False
+        self._ungated_step(idx, extra_grad, allreduce, mean, last)
+        return True
+
+    def _ungated_step(self, idx: Optional[torch.Tensor], extra_grad: float, allreduce, mean: bool, last: bool) -> None:
+        p = self.p
         if allreduce is None and self.can_fuse_apply(extra_grad):
             self.grad(idx, apply=True)          # world size 1: gather + Adam in one launch
             return
@@ -1516,6 +1508,8 @@ class HipEngine:
     def finish_steps(self) -> None:
         """apply a value-head step still waiting for its all-reduce (end of the epochs)"""
         self._flush_value()
+
+    quiesce = finish_steps    # (nothing else is ever deferred here: the parameters are then the synchronous ones)
 
     def metrics_stream(self) -> Optional[torch.cuda.Stream]:
         """the stream the iteration's metrics are packed and staged on: the side stream while the
@@ -1705,13 +1699,16 @@ class HipEngine:
         self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_whole], self.max_norm, self._next_step())
         self._stepped(self.norm_n_whole)
 
-    def pack_metrics(self, ep2: torch.Tensor) -> Optional[torch.Tensor]:
+    def pack_metrics(self, ep2: torch.Tensor, reduce=None) -> Optional[torch.Tensor]:
         """device f64[11] = [episode return sum, count | loss sums (8) | grad norm], written by ONE
         launch (csrc/optim.hip metrics_pack, 256 threads over the Adam partials) instead of ~6
-        small torch ops per iteration; the buffer is reused (stream order keeps the previous D2H
-        copy ahead of the next pack)."""
+        small torch ops per iteration, then the tails of ``self.metrics_layout``; the buffer is reused (stream
+        order keeps the previous D2H copy ahead of the next pack).  ``reduce``: the worker's all-reduce
+        for an ``ep2`` not yet summed over the ranks."""
         if self._loss_dev is None:
             return None
+        if reduce is not None:
+            ep2 = reduce(ep2)
         # every Adam path (fused no-clip, sumsq + clip, per head) leaves the per-block
         # sums of squares of the gradient it applied in norm_part[:_norm_n].  A value step left
         # pending on the process-group chains has not written its region yet: the norm is the
@@ -1725,29 +1722,37 @@ class HipEngine:
             side.wait_stream(torch.cuda.current_stream(self.device))
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
             self.ext.metrics_pack(ep2, self._loss_dev, self.norm_part[:n], self.metrics_buf)
-            if self.ret_stats is not None:      # return_std = sqrt(M2 / n) rides behind the 11
-                tail = self.metrics_buf[self._m_ret:self._m_ret + 1]
+            lay, buf = self.metrics_layout, self.metrics_buf
+            if self.ret_stats is not None:      # return_std = sqrt(M2 / n)
+                tail = buf[lay["return_std"]]
                 torch.mul(self.ret_stats.mean_diff, 1.0 / max(self.ret_stats.n, 1.0), out=tail)
                 tail.sqrt_()
             if self.gate is not None:           # [stop, applied, trip_kl | steps applied since the start]
-                g0 = self._m_gate
-                self.metrics_buf[g0:g0 + 3].copy_(self.gate[:3])
-                self.metrics_buf[g0 + 3:g0 + 4].copy_(self.adam_state[0:1])
-            if self.lr_state is not None:       # [lr, downs, ups] behind the gate tail
-                self.metrics_buf[self._m_lr:self._m_lr + 3].copy_(self.lr_state[:3])
-            elif self._m_adv > self._m_lr:                  # linear: the iteration's host rate
-                self.metrics_buf[self._m_lr:self._m_adv].fill_(self.lr)
-            if self.adv_scope:                  # [adv_mean, adv_std, explained_variance] behind the lr tail
-                a0 = self._m_adv
-                self.metrics_buf[a0:a0 + 1].copy_(self.adv_block[0:1])
-                self.metrics_buf[a0 + 1:a0 + 3].copy_(self.adv_block[2:4])
+                g = buf[lay["gate"]]
+                g[:3].copy_(self.gate[:3])
+                g[3:].copy_(self.adam_state[0:1])
+            if self.lr_state is not None:       # [lr, downs, ups]
+                buf[lay["lr"]].copy_(self.lr_state[:3])
+            elif self.p.lr_schedule == "linear":            # the iteration's host rate
+                buf[lay["lr"]].fill_(self.lr)
+            if self.adv_scope:                  # [adv_mean, adv_std, explained_variance]
+                a = buf[lay["adv"]]
+                a[:1].copy_(self.adv_block[0:1])
+                a[1:].copy_(self.adv_block[2:4])
         return self.metrics_buf
 
-    def lr_tail(self) -> torch.Tensor:
-        """the metrics vector's rate slots where pack_metrics does not run: [lr, downs, ups] (adaptive) or [lr]"""
-        if self.lr_state is not None:
-            return self.lr_state[:3]
-        return torch.tensor([self.lr], dtype=torch.float64)
+    def metrics_tails(self) -> Dict[str, torch.Tensor]:
+        """the metrics vector's tails by field name, where pack_metrics does not run"""
+        out = {}
+        if self.ret_stats is not None:
+            out["return_std"] = self.ret_stats.std()
+        if self.gate is not None:
+            out["gate"] = torch.cat([self.gate[:3], self.adam_state[0:1]])
+        if self.p.lr_schedule != "constant":
+            out["lr"] = self.lr_state[:3] if self.lr_state is not None else torch.tensor([self.lr], dtype=torch.float64)
+        if self.adv_scope:
+            out["adv"] = torch.cat([self.adv_block[0:1], self.adv_block[2:4]])
+        return out
 
     def lr_state_dict(self) -> torch.Tensor:
         return self.lr_state.detach().cpu()

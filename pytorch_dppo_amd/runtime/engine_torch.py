@@ -5,7 +5,7 @@ One *engine* owns the device-side state of one DPPO worker — the vectorised en
 ``[T,E]`` rollout buffer, the flat parameters / gradient / Adam moments — and exposes the
 phases the worker loop (``runtime/worker.py``) sequences:
 
-    rollout()  ->  values()  ->  gae()  ->  for each minibatch: grad(idx) -> [all-reduce] -> apply()
+    rollout()  ->  values()  ->  gae()  ->  for each minibatch: step(idx) = grad(idx) -> [all-reduce] -> apply()
 
 Reference mapping: rollout = ``train.py:60-106``; values/bootstrap = ``train.py:109-112``;
 gae = ``train.py:117-122``; grad = ``train.py:140-166``; apply = ``chief.py:15-19``.
@@ -24,9 +24,10 @@ from ..ops import oracle
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
 from ..utils.ret_stats import RunningReturnStats
+from .engine import Engine
 
 
-class TorchEngine:
+class TorchEngine(Engine):
     name = "torch"
 
     def __init__(self, params: Params, model: ActorCritic, env, stats: RunningObsStats,
@@ -92,6 +93,7 @@ class TorchEngine:
         self.key_action = rng.base_key(params.seed, rng.STREAM_ACTION, action_rank)
         self.obs = env.reset().to(device)
         self.local_stats: Optional[RunningObsStats] = None
+        self._pending = None          # (async all-reduce work, extra) of a step deferred under --overlap-rollout
 
     # -- rollout ---------------------------------------------------------------------------
     @torch.no_grad()
@@ -201,10 +203,6 @@ class TorchEngine:
     def set_adv_sums(self, sums: torch.Tensor, n: float) -> None:
         self.adv_block = oracle.adv_block(sums, n)
 
-    def adv_tail(self) -> torch.Tensor:
-        """the metrics vector's [adv_mean, adv_std, explained_variance] of the raw whole-buffer advantages"""
-        return self.adv_block[[0, 2, 3]].to(torch.float64)
-
     def current_obs(self) -> torch.Tensor:
         return self.obs
 
@@ -310,9 +308,61 @@ class TorchEngine:
             st[1 if d < 0 else 2] += 1.0
         self.lr = st[0]
 
-    def lr_tail(self) -> torch.Tensor:
-        """the metrics vector's rate slots: [lr, downs, ups] (adaptive) or [lr]"""
-        return torch.tensor(self.lr_state[:3] if self.lr_state is not None else [self.lr], dtype=torch.float64)
+    # -- one global step ------------------------------------------------------------------------
+    def step(self, idx: Optional[torch.Tensor], extra_grad: float = 0.0, allreduce=None,
+             mean: bool = False, last: bool = False) -> bool:
+        """ONE global step (runtime/engine.py): grad(idx), the all-reduce, apply().  --overlap-rollout: the
+        iteration's last step stays deferred — its all-reduce runs beside the next rollout and finish_steps()
+        applies it (a 1-update policy lag, safe for PPO because logp_old is recorded at rollout)."""
+        p = self.p
+        self.grad(idx)
+        if self.gate is not None:
+            # target_kl (ops/oracle.kl_gate): the step is applied while the gate is open, then the gate sees its KL
+            self._reduce(allreduce, self.grad_flat, mean)
+            self._reduce(allreduce, self.kl_pair, False)
+            if self.gate[0] == 0.0:
+                self.apply(extra_grad)
+            else:
+                self.skip()
+            self.gate, applied = oracle.kl_gate(self.kl_pair[0], self.kl_pair[1], p.gate_target(), self.gate)
+            if applied and self.lr_state is not None:
+                self.adapt(self.gate[3])           # the next step's rate (ops/oracle.lr_adapt)
+            return applied
+        if p.overlap_rollout and last and not mean and allreduce is not None:
+            self._pending = (allreduce(self.grad_flat), extra_grad)
+            return True
+        self._reduce(allreduce, self.grad_flat, mean)
+        self.apply(extra_grad)
+        return True
+
+    def _reduce(self, allreduce, t: torch.Tensor, mean: bool) -> None:
+        """``t`` summed (``mean``: averaged) over the ranks in place; no collective: untouched"""
+        if allreduce is None:
+            return
+        allreduce(t).wait()
+        if mean:
+            t.mul_(1.0 / torch.distributed.get_world_size())
+
+    def finish_steps(self) -> None:
+        """apply the step step() left deferred, if any"""
+        pend, self._pending = self._pending, None
+        if pend is not None:
+            work, extra = pend
+            work.wait()
+            self.apply(extra)
+
+    def metrics_tails(self) -> Dict[str, torch.Tensor]:
+        """the metrics vector's tails by field name (runtime/metrics_layout.py)"""
+        out = {}
+        if self.ret_stats is not None:
+            out["return_std"] = self.ret_stats.std()
+        if self.gate is not None:
+            out["gate"] = torch.tensor(list(self.gate[:3]) + [float(self.adam_step)], dtype=torch.float64)
+        if self.p.lr_schedule != "constant":
+            out["lr"] = torch.tensor(self.lr_state[:3] if self.lr_state is not None else [self.lr], dtype=torch.float64)
+        if self.adv_scope:                 # of the raw whole-buffer advantages
+            out["adv"] = self.adv_block[[0, 2, 3]]
+        return out
 
     def lr_state_dict(self) -> torch.Tensor:
         return torch.tensor(self.lr_state, dtype=torch.float32)

@@ -46,11 +46,10 @@ def run_worker(params: Params, ctx: DistContext, max_iters: Optional[int] = None
         if st is not None:
             w.load_trainer_state(st)
         es = ckpt.load_env_state(params.resume, ctx.rank)
-        if es is not None and hasattr(w.engine, "load_env_state"):
+        if es is not None:
             w.engine.load_env_state(es)
         ctx.broadcast_(w.model.flat.data, src=0)
-        if hasattr(w.engine, "params_changed"):
-            w.engine.params_changed()
+        w.engine.params_changed()
     ev = None
     # eval_mode inline: rank 0 evaluates in its own engine (no evaluator process, no collective —
     # the other ranks meet rank 0 at the next all-reduce as usual)
@@ -149,10 +148,8 @@ def save(w, ctx: DistContext, path: str) -> None:
     # every deferred step applied BEFORE the weights are copied out: model.pt and the Adam state
     # of trainer_state.pt must describe the same step
     w.flush_pending()
-    if hasattr(w.engine, "raise_if_failed"):
-        w.engine.raise_if_failed(sync=True)   # never checkpoint a step built on a failed launch
-    env_state = w.engine.env_state() if hasattr(w.engine, "env_state") else None
-    ckpt.save_checkpoint(path, w.model.state_dict(), w.trainer_state(), ctx.rank, env_state)
+    w.engine.raise_if_failed(sync=True)   # never checkpoint a step built on a failed launch
+    ckpt.save_checkpoint(path, w.model.state_dict(), w.trainer_state(), ctx.rank, w.engine.env_state())
     ctx.barrier()
 
 

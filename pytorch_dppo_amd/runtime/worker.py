@@ -16,7 +16,6 @@ busy-spin (Q14) disappear: a step costs compute + one collective.
 from __future__ import annotations
 
 import contextlib
-import json
 import math
 import os
 import sys
@@ -29,11 +28,10 @@ import torch
 from ..config import Params
 from ..envs import get_spec, host_spec, import_env_module, make_vec_env
 from ..models.actor_critic import ActorCritic
-from ..ops import oracle
 from ..parallel.dist import DistContext
-from ..utils import rng
 from ..utils.metrics import MetricsLogger, PhaseTimer
 from ..utils.obs_stats import RunningObsStats
+from .metrics_layout import MetricsLayout
 
 
 def build_engine(params: Params, model, env, stats, device, action_rank):
@@ -68,7 +66,7 @@ class DPPOWorker:
                                     device=self.device, max_episode_length=params.max_episode_length)
         self.stats = RunningObsStats(self.spec.obs_dim, self.device)
         self.engine = build_engine(params, self.model, self.env, self.stats, self.device, action_rank)
-        if ctx.collective and hasattr(self.engine, "ext"):
+        if ctx.collective and self.engine.ext is not None:
             # in-stream communicator (collective: every rank); --overlap-rollout also gets the
             # side-stream one its deferred value step uses
             ctx.init_native_comm(self.engine.ext, side=bool(params.overlap_rollout or params.overlap_value_epochs))
@@ -88,7 +86,8 @@ class DPPOWorker:
             fr, fi, fe = (int(x) for x in spec.split(":"))
             if fr == ctx.rank:
                 self._fault = (fi, fe)
-        self._pending = None          # (async all-reduce work, extra) under --overlap-rollout
+        # the metrics vector's layout, by whether the loss vector rides in it (engine.loss_vector() is not None)
+        self._layouts = {h: MetricsLayout(params, has_loss=h) for h in (False, True)}
         self._staged = None           # metrics of the last deferred iteration (iteration_step(defer=True))
         self._staged_evals: list = [] # inline evaluations enqueued, not yet read (stage_eval / resolve_evals)
         self.eval_history: list = []  # their records, oldest first
@@ -102,7 +101,7 @@ class DPPOWorker:
         # than the ~15 us (+ all-reduce latency) they hide.
         want = {"on": True, "off": False}.get(params.stats_stream, bool(ctx.collective))
         self._stats_stream = None
-        if want and self.device.type == "cuda" and hasattr(self.engine, "s12"):
+        if want and self.device.type == "cuda" and self.engine.has_stats_stream:
             self._stats_stream = torch.cuda.Stream(device=self.device)
 
     # ---------------------------------------------------------------------------------------
@@ -145,12 +144,9 @@ class DPPOWorker:
         tm.start("rollout")
         side = self._stats_stream if p.obs_norm_update == "rollout" else None
         ro = eng.rollout(stats_stream=side) if side is not None else eng.rollout()
-        # --overlap-rollout: the previous iteration's final gradient all-reduce ran on
-        # RCCL's stream concurrently with the rollout just enqueued.  GPU engine (per-head
-        # chains): only the VALUE head's last step was left pending — the rollout reads only the
-        # policy, so this is exact; apply it now, before values() reads the value head.  CPU
-        # engine: the whole last step (a 1-update policy lag, safe for PPO because logp_old is
-        # recorded at rollout).
+        # --overlap-rollout: the step the engine left deferred ran its all-reduce beside the
+        # rollout just enqueued (GPU engine: the VALUE head's last step, exact — the rollout reads only the
+        # policy; CPU engine: the whole last step); apply it now, before values() reads the value head
         self.flush_pending()
         tm.stop("rollout")
         tm.start("obs_stats")
@@ -174,8 +170,6 @@ class DPPOWorker:
                 stats_done.record(side)
         else:
             self._merge_stats(ro["count"], ro["s1"], ro["s2"], ro["shift"], count_uniform=True, extra=ep_extra)
-        if p.obs_norm_update == "step" and hasattr(eng, "after_stats_merge"):
-            eng.after_stats_merge()
         if rs12 is not None:
             eng.merge_return_moments(float(eng.T * eng.E * (self.ctx.world_size if self.ctx.collective else 1)), rs12)
         tm.stop("obs_stats")
@@ -200,8 +194,7 @@ class DPPOWorker:
         eng.begin_update()
         N, mb, nmb = self._minibatch_plan()
         mean = p.grad_reduce == "mean"
-        gated = p.gated()
-        adaptive = p.lr_schedule == "adaptive"
+        ar = self.ctx.grad_allreduce_fn(mean)     # in stream order (native RCCL, the gloo adapter), or an async work
         self._perm_gen.manual_seed((p.seed * 1000003 + self.ctx.rank * 7919 + self.iteration) & 0x7FFFFFFF)
         for epoch in range(p.num_epoch):
             if mb >= N and nmb == 1:
@@ -224,41 +217,10 @@ class DPPOWorker:
                     print(f"[dppo rank {self.ctx.rank}] DPPO_DEBUG_FAULT: exiting at iteration {self.iteration} "
                           f"epoch {epoch}", file=sys.stderr, flush=True)
                     os._exit(13)
-                if hasattr(eng, "step"):
-                    # GPU engine: gradient -> all-reduce -> Adam.  In-stream communicator (the
-                    # default: native RCCL, or the gloo adapter): in stream order after the joint
-                    # gather (the last step's value half on the side stream under
-                    # --overlap-rollout); a process-group all-reduce: per-head chains, each head's
-                    # async all-reduce overlapping the other head's kernels (HipEngine.step)
-                    ar = self.ctx.grad_allreduce_fn(mean)
-                    eng.step(idx, extra, allreduce=ar, mean=mean, last=last)
-                    if not gated:     # (target_kl: the device counts the applied steps)
-                        self.updates += 1
-                    continue
-                deferred = p.overlap_rollout and last and not mean and self.ctx.collective
-                eng.grad(idx)
-                if gated:
-                    # target_kl (ops/oracle.kl_gate): the gradient and the KL pair are summed over the
-                    # ranks; the step is applied while the gate is open, then the gate sees its KL
-                    self.ctx.allreduce_grads(eng.grad_flat, mean=mean)
-                    pair = self.ctx.allreduce_tensor_(eng.kl_pair)
-                    if eng.gate[0] == 0.0:
-                        eng.apply(extra)
-                        self.updates += 1
-                    else:
-                        eng.skip()
-                    eng.gate, applied = oracle.kl_gate(pair[0], pair[1], p.gate_target(), eng.gate)
-                    if adaptive and applied:
-                        eng.adapt(eng.gate[3])         # the next step's rate (ops/oracle.lr_adapt)
-                    continue
-                if deferred:
-                    work = self.ctx.allreduce_grads(eng.grad_flat, async_op=True)
-                    self._pending = (work, extra)      # applied after the next rollout launch
-                else:
-                    self.ctx.allreduce_grads(eng.grad_flat, mean=mean)
-                    eng.apply(extra)
-                self.updates += 1
-        if hasattr(eng, "finish_steps") and not (p.overlap_rollout and self.ctx.collective):
+                # gradient -> all-reduce -> Adam; True: the host counts an applied update (runtime/engine.py)
+                if eng.step(idx, extra, allreduce=ar, mean=mean, last=last):
+                    self.updates += 1
+        if not (p.overlap_rollout and self.ctx.collective):
             eng.finish_steps()        # the last value-head step's all-reduce + Adam
         if stats_done is not None:
             # order the compute stream after the merge: the metrics read the episode stats, and
@@ -270,23 +232,14 @@ class DPPOWorker:
         self.env_steps += steps_local * self.ctx.world_size
         self.iteration += 1
         staged = self._stage_metrics(ro, t0, steps_local)
-        if not defer:
-            m = self._resolve_metrics(staged)
-            self.last_metrics = m
-            return m
-        prev, self._staged = self._staged, staged
-        m = self._resolve_metrics(prev) if prev is not None else {}
-        if m:
-            self.last_metrics = m
-        return m
+        if defer:
+            staged, self._staged = self._staged, staged
+        return self._resolve_metrics(staged)
 
     def finish_metrics(self) -> Dict:
         """resolve the metrics still staged by a deferred ``iteration_step`` (or {})."""
         prev, self._staged = self._staged, None
-        m = self._resolve_metrics(prev) if prev is not None else {}
-        if m:
-            self.last_metrics = m
-        return m
+        return self._resolve_metrics(prev)
 
     def _stage_metrics(self, ro: Dict, t0: float, steps_local: int) -> Dict:
         """Device-side metric values of this iteration -> one pinned host buffer (async)."""
@@ -294,73 +247,53 @@ class DPPOWorker:
         dev = self.device
         ep2 = ro.get("ep2")
         flat = None
-        if ep2 is not None and hasattr(eng, "pack_metrics") and getattr(eng, "_loss_dev", None) is not None:
-            # GPU engine: the [return sum, count] pair (R5) was summed over ranks with the
-            # observation moments (or is all-reduced here), then one launch packs it with the
-            # loss sums and the gradient norm
-            flat = eng.pack_metrics(ep2 if ro.get("ep2_reduced") else self.ctx.allreduce_tensor_(ep2))
-        if flat is not None:
-            loss_dev = flat
-        else:
-            flat, loss_dev = self._stage_parts(ro)
-            if self.p.reward_norm:     # return_std rides behind the vector (pack_metrics wrote its own)
-                flat = torch.cat([flat, eng.ret_stats.std().to(flat.device)])
-            if self.p.gated():         # [stop, applied, trip_kl | steps applied since the start], likewise
-                if torch.is_tensor(eng.gate):      # (the GPU engine without a device rollout's ep2)
-                    tail = torch.cat([eng.gate[:3], eng.adam_state[0:1]])
-                else:
-                    tail = torch.tensor(list(eng.gate[:3]) + [float(self.updates)], dtype=torch.float64)
-                flat = torch.cat([flat, tail.to(flat.device, torch.float64)])
-            if self.p.lr_schedule != "constant":   # [lr, downs, ups] (adaptive) or [lr] (linear), behind the gate tail
-                flat = torch.cat([flat, eng.lr_tail().to(flat.device, torch.float64)])
-            if self.p.adv_scope():     # [adv_mean, adv_std, explained_variance], behind the lr tail
-                flat = torch.cat([flat, eng.adv_tail().to(flat.device, torch.float64)])
-        if dev.type == "cuda":
-            # the stream the metrics were packed on (the side stream while the overlapped value
-            # step runs there)
-            side = eng.metrics_stream() if hasattr(eng, "metrics_stream") else None
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                host = torch.empty(flat.numel(), dtype=torch.float64, pin_memory=True)
-                host.copy_(flat, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-        else:
-            host, ev = flat, None
-        return {"host": host, "event": ev, "phases": self.timer.collect(), "has_loss": loss_dev is not None,
+        if ep2 is not None:
+            # GPU engine: the [return sum, count] pair (R5) was summed over ranks with the observation moments
+            # (or is all-reduced here), then one launch packs it with the loss sums and the gradient norm
+            flat = eng.pack_metrics(ep2, None if ro.get("ep2_reduced") else self.ctx.allreduce_tensor_)
+        lay = self._layouts[True]
+        if flat is None:
+            # the CPU engine (and the GPU engine while it has no loss vector yet): the same layout, filled here
+            ep = torch.stack([torch.as_tensor(ro["ep_return_sum"], dtype=torch.float64, device=dev).reshape(()),
+                              torch.as_tensor(ro["ep_count"], dtype=torch.float64, device=dev).reshape(())])
+            loss = eng.loss_vector()
+            lay = self._layouts[loss is not None]
+            flat = torch.zeros(lay.size, dtype=torch.float64, device=dev)
+            flat[lay["ep"]] = self.ctx.allreduce_tensor_(ep)       # R5: episode stats over ranks
+            if loss is not None:
+                flat[lay["loss"]] = loss
+            for name, t in eng.metrics_tails().items():
+                flat[lay[name]] = t
+        # on the stream the metrics were packed on (the side stream while the overlapped value step runs there)
+        host, ev = self._to_host(flat, eng.metrics_stream())
+        return {"host": host, "event": ev, "phases": self.timer.collect(), "layout": lay,
                 "iteration": self.iteration, "env_steps": self.env_steps, "updates": self.updates,
                 "host_s": time.perf_counter() - t0, "steps_local": steps_local}
 
-    def _stage_parts(self, ro: Dict):
-        """generic staging (CPU engine): [ep return sum, count] (+ loss vector) as one f64 tensor."""
-        eng = self.engine
-        dev = self.device
-        parts = [torch.stack([torch.as_tensor(ro["ep_return_sum"], dtype=torch.float64, device=dev).reshape(()),
-                              torch.as_tensor(ro["ep_count"], dtype=torch.float64, device=dev).reshape(())])]
-        parts[0] = self.ctx.allreduce_tensor_(parts[0])        # R5: episode stats over ranks
-        loss_dev = eng.loss_vector() if hasattr(eng, "loss_vector") else None
-        if loss_dev is not None:
-            parts.append(loss_dev.to(torch.float64))
-        return torch.cat([x.reshape(-1) for x in parts]), loss_dev
+    def _to_host(self, vec: torch.Tensor, side=None):
+        """(pinned host copy of the device vector ``vec``, the event behind the async copy); CPU: (vec, None)"""
+        if self.device.type != "cuda":
+            return vec, None
+        with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
+            host = torch.empty(vec.numel(), dtype=torch.float64, pin_memory=True)
+            host.copy_(vec, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        return host, ev
 
-    def _resolve_metrics(self, st: Dict) -> Dict:
+    def _resolve_metrics(self, st: Optional[Dict]) -> Dict:
+        """the record of a staged iteration, kept as ``last_metrics`` ({}: nothing was staged)"""
+        if st is None:
+            return {}
         p = self.p
         if st["event"] is not None:
             self.ctx.wait_event(st["event"])     # bounded by dist_timeout_s (collective watchdog)
-        if hasattr(self.engine, "raise_if_failed"):
-            self.engine.raise_if_failed()        # (a timed-out per-step filter launch: never report it)
-        v = st["host"].tolist()
-        kl_gate = lr_tail = adv_tail = None
-        if p.adv_scope():
-            adv_tail, v = v[-3:], v[:-3]
-        if p.lr_schedule != "constant":
-            k = 3 if p.lr_schedule == "adaptive" else 1
-            lr_tail, v = v[-k:], v[:-k]
-        if p.gated():
-            kl_gate, v = v[-4:], v[:-4]
-        ret_std = v.pop() if p.reward_norm else None
-        ep_ret, ep_cnt = v[0], v[1]
-        if st["has_loss"]:
-            losses = self.engine.losses_from_vector(v[2:])
+        self.engine.raise_if_failed()            # (a timed-out per-step filter launch: never report it)
+        f = st["layout"].decode(st["host"].tolist())
+        ep_ret, ep_cnt = f["ep"]
+        kl_gate, lr_tail, adv_tail = f["gate"], f["lr"], f["adv"]
+        if f["loss"] is not None:
+            losses = self.engine.losses_from_vector(f["loss"])
         else:
             losses = self.engine.last_losses()
         gnorm = losses.pop("grad_norm", 0.0)
@@ -371,8 +304,8 @@ class DPPOWorker:
              "iter_s": dt, "steps_per_s": st["steps_local"] * self.ctx.world_size / max(dt, 1e-9),
              "ep_count": ep_cnt, "mean_ep_return": (ep_ret / ep_cnt) if ep_cnt > 0 else float("nan"),
              "grad_norm": gnorm, **losses, **phases}
-        if ret_std is not None:
-            m["return_std"] = ret_std
+        if f["return_std"] is not None:
+            m["return_std"] = f["return_std"][0]
         if kl_gate is not None:
             # target_kl: `updates` is the cumulative number of steps APPLIED (the device's counter)
             stopped = kl_gate[0] != 0.0
@@ -382,7 +315,7 @@ class DPPOWorker:
         if lr_tail is not None:
             # lr_schedule: the rate the iteration ended with; adaptive: the cumulative decisions too
             m["lr"] = lr_tail[0]
-            if len(lr_tail) == 3:
+            if p.lr_schedule == "adaptive":
                 m.update(lr_downs=int(lr_tail[1]), lr_ups=int(lr_tail[2]))
         if adv_tail is not None:
             # adv_norm_scope global | minibatch: of the raw advantages of the whole buffer (global: every rank's);
@@ -394,6 +327,7 @@ class DPPOWorker:
             m["replicas_in_sync"] = self.ctx.verify_replicas(self.model.flat.data)
         if p.check_finite:
             self._check_finite(m)
+        self.last_metrics = m
         return m
 
     def _check_finite(self, m: Dict) -> None:
@@ -422,13 +356,7 @@ class DPPOWorker:
         ret, length = self.engine.evaluate(p.eval_envs, bool(p.eval_deterministic))
         r = ret.to(torch.float64)
         vec = torch.stack([r.mean(), r.std(unbiased=False), r.min(), r.max(), length.to(torch.float64).mean()])
-        if self.device.type == "cuda":
-            host = torch.empty(vec.numel(), dtype=torch.float64, pin_memory=True)
-            host.copy_(vec, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        else:
-            host, ev = vec, None
+        host, ev = self._to_host(vec)
         self._staged_evals.append({"host": host, "event": ev, "iteration": self.iteration,
                                    "episodes": int(ret.numel())})
 
@@ -442,8 +370,7 @@ class DPPOWorker:
         for st in staged:
             if st["event"] is not None:
                 self.ctx.wait_event(st["event"])
-            if hasattr(self.engine, "raise_if_failed"):
-                self.engine.raise_if_failed()    # (behind a timed-out per-step filter launch: never report it)
+            self.engine.raise_if_failed()        # (behind a timed-out per-step filter launch: never report it)
             v = st["host"].tolist()
             rec = {"eval_iteration": int(st["iteration"]), "eval_return_mean": v[0], "eval_return_std": v[1],
                    "eval_return_min": v[2], "eval_return_max": v[3], "eval_length_mean": v[4],
@@ -458,24 +385,14 @@ class DPPOWorker:
         return out
 
     def quiesce(self) -> None:
-        """the GPU engine's deferred value-head step (side stream / pending all-reduce) applied:
-        the parameters are the synchronous ones (snapshots, checksums); the CPU engine's deferred
-        whole step (its documented 1-update lag) is left alone"""
-        if hasattr(self.engine, "finish_steps"):
-            self.engine.finish_steps()
+        """the parameters are the synchronous ones (snapshots, checksums): the GPU engine's deferred
+        value-head step (side stream / pending all-reduce) applied; the CPU engine's deferred whole
+        step (its documented 1-update lag) is left alone"""
+        self.engine.quiesce()
 
     def flush_pending(self) -> None:
         """complete a deferred (overlapped) all-reduce + Adam step, if any."""
-        if hasattr(self.engine, "finish_steps"):
-            self.engine.finish_steps()
-        pend = getattr(self, "_pending", None)
-        if pend is None:
-            return
-        work, extra = pend
-        self._pending = None
-        if work is not None:
-            work.wait()            # orders the compute stream after RCCL's (no host block on GPU)
-        self.engine.apply(extra)
+        self.engine.finish_steps()
 
     def should_stop(self) -> bool:
         p = self.p
@@ -505,7 +422,7 @@ class DPPOWorker:
                 # fp8 mode's e4m3 wgrad operands: the gradient-maxima ring the next step's delayed
                 # scales come from (a resumed run continues bit-identically)
                 **({"q8_amax": eng.q8_amax.detach().cpu(), "q8_next": eng._q8_next}
-                   if getattr(eng, "q8", False) else {})}
+                   if eng.q8 else {})}
 
     def load_trainer_state(self, st: Dict) -> None:
         eng = self.engine
@@ -529,9 +446,8 @@ class DPPOWorker:
             else:
                 warnings.warn("lr_schedule=adaptive: the checkpoint has no lr_state; the rate starts at lr", UserWarning,
                               stacklevel=2)
-        if getattr(eng, "q8", False) and "q8_amax" in st:
+        if eng.q8 and "q8_amax" in st:
             eng.q8_amax.copy_(st["q8_amax"].to(eng.q8_amax.device))
             eng._q8_next = int(st["q8_next"])
             eng._q8_cal = [True, True]
-        if hasattr(eng, "params_changed"):
-            eng.params_changed()
+        eng.params_changed()

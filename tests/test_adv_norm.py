@@ -195,8 +195,7 @@ def _zero_value_output(w):
     """V == 0 everywhere: the advantages are then a function of the rewards alone"""
     for k in ("v.weight", "v.bias"):
         w.model.view(k).data.zero_()
-    if hasattr(w.engine, "params_changed"):
-        w.engine.params_changed()
+    w.engine.params_changed()
 
 
 def first_policy_grad(k, device="cpu", **kw):
