@@ -789,9 +789,53 @@ SlabRuns make_runs(const std::vector<int64_t>& v, int64_t n) {
   return r;
 }
 
+// The optional tile table of a gather (csrc/kernels.h SlabTiles): `tiles` on the device, `tiles_host` its CPU
+// mirror (like wgrad's task list), checked here on every call — every quad's chunk loads stay inside the slab
+// and every flat element inside [0, n).  Both absent (or empty): the per-element form.
+using OptTensor = const std::optional<torch::Tensor>&;
+SlabTiles slab_tiles(OptTensor tiles, OptTensor tiles_host, CT slab, const SlabRuns& runs, int64_t n) {
+  SlabTiles st{};
+  if (!tiles.has_value() || !tiles->defined() || tiles->numel() == 0) return st;
+  TORCH_CHECK(tiles_host.has_value() && tiles_host->defined(), "a tile table needs its CPU mirror tiles_host");
+  const int64_t nt = tiles->numel() / SLAB_TILE_INTS;
+  check(*tiles, "tiles", at::kInt, 1);
+  TORCH_CHECK(nt >= 1 && nt <= SLAB_TILES_MAX && tiles->numel() == nt * SLAB_TILE_INTS, "tiles: 1-", SLAB_TILES_MAX,
+              " records of ", SLAB_TILE_INTS, " ints");
+  TORCH_CHECK(!tiles_host->is_cuda() && tiles_host->scalar_type() == at::kInt && tiles_host->numel() == tiles->numel(),
+              "tiles_host must mirror tiles on CPU");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(slab.data_ptr<float>()) % 16 == 0, "slab must be 16-byte aligned");
+  auto th = tiles_host->contiguous();
+  const int* t = th.data_ptr<int>();
+  const int64_t slab_n = slab.numel();
+  int64_t quads = 0, elems = 0;
+  for (int64_t u = 0; u < nt; ++u) {
+    const int* e = t + u * SLAB_TILE_INTS;
+    const int64_t base = e[0], nch = e[1], stride = e[2], n0 = e[3], k0 = e[4], kq = e[5], fan_in = e[6],
+                  fan_out = e[7], w_off = e[8], b_off = e[9], nq = e[10];
+    TORCH_CHECK(nq >= 1 && kq >= 1 && nch >= 1 && fan_in >= 1 && n0 >= 0 && n0 < fan_out && k0 >= 0 && k0 <= fan_in,
+                "tiles[", u, "]: bad tile shape");
+    const int64_t size = nq * kq * 4096;
+    TORCH_CHECK(base >= 0 && base % 4 == 0 && stride % 4 == 0 && stride >= size &&
+                    base + (nch - 1) * stride + size <= slab_n,
+                "tiles[", u, "] leaves the slab");
+    TORCH_CHECK(w_off >= 0 && w_off + fan_out * fan_in <= n && b_off >= 0 && b_off + fan_out <= n,
+                "tiles[", u, "] leaves the flat range");
+    TORCH_CHECK(e[11] == quads, "tiles[", u, "]: quad0 must be the running quad count");
+    quads += (int64_t)slab_tile_rows(e) * ((slab_tile_cols(e) + 3) / 4);
+    elems += (int64_t)slab_tile_rows(e) * slab_tile_cols(e);
+    TORCH_CHECK(quads < INT32_MAX, "too many quads");
+  }
+  TORCH_CHECK(elems == runs.total, "the tile table covers ", elems, " elements, the slab runs ", runs.total);
+  st.t = tiles->data_ptr<int>();
+  st.n = (int)nt;
+  st.nquads = (int)quads;
+  return st;
+}
+
 // GatherArgs (csrc/kernels.h) of a gather over a flat range of n elements, checked
 GatherArgs gather_args(CT slab, CT src_off, CT src_meta, CT part, int64_t npblk, int64_t npart, CT red_col, CT red_dst,
-                       const std::vector<int64_t>& runs, double scale, CT loss_out, int64_t n) {
+                       const std::vector<int64_t>& runs, double scale, CT loss_out, int64_t n,
+                       OptTensor tiles = std::nullopt, OptTensor tiles_host = std::nullopt) {
   check(src_off, "src_off", at::kInt, n);
   check(src_meta, "src_meta", at::kInt, n);
   check(slab, "slab", at::kFloat, 1);
@@ -814,16 +858,18 @@ GatherArgs gather_args(CT slab, CT src_off, CT src_meta, CT part, int64_t npblk,
   ga.runs = make_runs(runs, n);
   ga.scale = (float)scale;
   ga.loss_out = loss_out.data_ptr<float>();
+  ga.tiles = slab_tiles(tiles, tiles_host, slab, ga.runs, n);
   return ga;
 }
 
 void grad_gather(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_meta, torch::Tensor part,
                  int64_t nblk, int64_t npart, torch::Tensor red_col, torch::Tensor red_dst, double scale,
-                 torch::Tensor grad, torch::Tensor loss_out, std::vector<int64_t> runs) {
+                 torch::Tensor grad, torch::Tensor loss_out, std::vector<int64_t> runs, OptTensor tiles,
+                 OptTensor tiles_host) {
   const int64_t n = grad.numel();
   check(grad, "grad", at::kFloat, n);
-  const GatherArgs ga =
-      gather_args(slab, src_off, src_meta, part, nblk, npart, red_col, red_dst, runs, scale, loss_out, n);
+  const GatherArgs ga = gather_args(slab, src_off, src_meta, part, nblk, npart, red_col, red_dst, runs, scale,
+                                    loss_out, n, tiles, tiles_host);
   launch_grad_gather(ga, grad.data_ptr<float>(), cur_stream());
   after_launch(__func__);
 }
@@ -1136,11 +1182,11 @@ void gather_adam(torch::Tensor slab, torch::Tensor src_off, torch::Tensor src_me
                  torch::Tensor v, double lr, double b1, double b2, double eps, int64_t step, torch::Tensor state,
                  torch::Tensor norm_part, torch::Tensor wimg, torch::Tensor w_map, torch::Tensor wt_map, int64_t dt,
                  torch::Tensor qmul, torch::Tensor f8_img, torch::Tensor f8_lid, torch::Tensor f8_qs,
-                 torch::Tensor gate, OptT lr_dev) {
+                 torch::Tensor gate, OptT lr_dev, OptTensor tiles, OptTensor tiles_host) {
   const AdamArgs a = adam_args(p, g, m, v, lr, b1, b2, eps, 0.0, step, state, norm_part, wimg, w_map, wt_map, dt, qmul,
                                f8_img, f8_lid, f8_qs, gate, lr_dev);
-  const GatherArgs ga =
-      gather_args(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale, loss_out, p.numel());
+  const GatherArgs ga = gather_args(slab, src_off, src_meta, part, npblk, npart, red_col, red_dst, runs, scale,
+                                    loss_out, p.numel(), tiles, tiles_host);
   TORCH_CHECK(a.gate != nullptr || step >= 1, "gather_adam needs the host step number (eager launches only)");
   TORCH_CHECK(a.nblk > item_blocks(ga.nitems), "norm_part must hold more blocks than the reduce blocks");
   launch_gather_adam(ga, a, cur_stream());
@@ -1229,7 +1275,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_rollout_tstamp", &set_rollout_tstamp);
   m.def("wgrad", &wgrad);
   m.def("wgrad_task_ok", [](int64_t dt, int64_t nq, int64_t kq) { return wgrad_task_ok((int)dt, (int)nq, (int)kq) != 0; });
-  m.def("grad_gather", &grad_gather);
+  m.def("grad_gather", &grad_gather, pybind11::arg("slab"), pybind11::arg("src_off"), pybind11::arg("src_meta"),
+        pybind11::arg("part"), pybind11::arg("nblk"), pybind11::arg("npart"), pybind11::arg("red_col"),
+        pybind11::arg("red_dst"), pybind11::arg("scale"), pybind11::arg("grad"), pybind11::arg("loss_out"),
+        pybind11::arg("runs"), pybind11::arg("tiles") = pybind11::none(), pybind11::arg("tiles_host") = pybind11::none());
+  m.attr("slab_sum_batch") = SLAB_SUM_BATCH;
+  m.def("set_gather_stream", [](int64_t on) { set_gather_stream((int)on); });
   m.def("gae", &gae);
   m.def("gae_boot", &gae_boot);
   m.def("gae_rn", &gae_rn);
@@ -1254,7 +1305,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("loss_out"), py::arg("g"), py::arg("p"), py::arg("m"), py::arg("v"), py::arg("lr"), py::arg("b1"),
         py::arg("b2"), py::arg("eps"), py::arg("step"), py::arg("state"), py::arg("norm_part"), py::arg("wimg"),
         py::arg("w_map"), py::arg("wt_map"), py::arg("dt"), py::arg("qmul"), py::arg("f8_img"), py::arg("f8_lid"),
-        py::arg("f8_qs"), py::arg("gate"), py::arg("lr_dev") = py::none());
+        py::arg("f8_qs"), py::arg("gate"), py::arg("lr_dev") = py::none(), py::arg("tiles") = py::none(),
+        py::arg("tiles_host") = py::none());
   m.def("kl_gate", &kl_gate, py::arg("loss_sums"), py::arg("gate"), py::arg("state"), py::arg("target_kl"),
         py::arg("lr_state") = py::none(), py::arg("kl_target") = 0.0, py::arg("factor") = 0.0,
         py::arg("lr_min") = 0.0, py::arg("lr_max") = 0.0);

@@ -372,6 +372,78 @@ __device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nch, 
   return s;
 }
 
+// The streaming form of the same sums (kernels.h SlabTiles; docs/ARCHITECTURE.md §26).  A quad is
+// four consecutive k of one row n of a wgrad output tile: one aligned 16-byte load per chunk.
+struct SlabQuad {
+  const float4* src;   // the quad in the tile's chunk 0
+  int nch;             // chunks of its tile
+  size_t st4;          // chunk stride in 16-byte units
+  int i[4];            // flat element of each lane of the quad; -1: none (past the bias column)
+};
+
+// the block's copy of the tile table in LDS (tl: SLAB_TILES_MAX * SLAB_TILE_INTS ints)
+__device__ __forceinline__ void slab_tiles_stage(const SlabTiles& tiles, int* tl) {
+  for (int w = threadIdx.x; w < tiles.n * SLAB_TILE_INTS; w += blockDim.x) tl[w] = tiles.t[w];
+  __syncthreads();
+}
+
+// quad Q < tiles.nquads of the staged table: its source and its (up to) four flat elements, by
+// arithmetic alone — no per-element index load heads the chunk loads
+__device__ __forceinline__ SlabQuad slab_quad(const int* tl, int ntiles, int Q, const float* __restrict__ slab) {
+  int t = 0;
+  for (int u = 1; u < ntiles; ++u)
+    if (Q >= tl[u * SLAB_TILE_INTS + 11]) t = u;
+  const int* e = tl + t * SLAB_TILE_INTS;
+  const int fan_in = e[6], ld = e[5] * 64;
+  const int qr = (slab_tile_cols(e) + 3) >> 2;   // quads per tile row
+  const int ql = Q - e[11];
+  const int r = ql / qr, q4 = 4 * (ql - r * qr);
+  const int n = e[3] + r, k = e[4] + q4;
+  SlabQuad o;
+  o.src = reinterpret_cast<const float4*>(slab + (size_t)e[0] + (size_t)r * ld + q4);
+  o.nch = e[1];
+  o.st4 = (size_t)(e[2] >> 2);
+#pragma unroll
+  for (int l = 0; l < 4; ++l) o.i[l] = k + l < fan_in ? e[8] + n * fan_in + k + l : (k + l == fan_in ? e[9] + n : -1);
+  return o;
+}
+
+// per lane of the quad, sum_{c < nch} chunk c in that fixed order — slab_sum's sum — as a stream:
+// two buffers of B = SLAB_SUM_BATCH 16-byte loads, the next batch issued before the current batch's adds
+__device__ __forceinline__ float4 slab_sum4(const float4* __restrict__ p, int nch, size_t st4) {
+  constexpr int B = SLAB_SUM_BATCH;
+  float4 a[B], b[B];
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  // every load issues (a slot past the last chunk re-reads the last chunk and is not added): a load
+  // under a branch would leave the counter of loads in flight unknown, and every wait a full drain
+  auto load = [&](float4 (&x)[B], int c0) {
+#pragma unroll
+    for (int c = 0; c < B; ++c) x[c] = p[(size_t)min(c0 + c, nch - 1) * st4];
+  };
+  auto add = [&](const float4 (&x)[B], int c0) {
+#pragma unroll
+    for (int c = 0; c < B; ++c) {
+      const bool on = c0 + c < nch;
+      s0 = on ? s0 + x[c].x : s0;
+      s1 = on ? s1 + x[c].y : s1;
+      s2 = on ? s2 + x[c].z : s2;
+      s3 = on ? s3 + x[c].w : s3;
+    }
+  };
+  load(a, 0);
+  for (int c0 = 0; c0 < nch; c0 += 2 * B) {
+    load(b, c0 + B);
+    __builtin_amdgcn_sched_barrier(0);   // (the next batch's loads stay ahead of this batch's adds)
+    add(a, c0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(a, c0 + 2 * B);
+    __builtin_amdgcn_sched_barrier(0);
+    add(b, c0 + B);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return float4{s0, s1, s2, s3};
+}
+
 // Column sums of the per-workgroup partial rows (the reduce items of the gather kernels): the
 // 256 threads of a block take items j = IPB b + (tid % IPB) (consecutive items are consecutive
 // columns: one 128-byte segment per row) in RG = 256 / IPB row groups; row group g sums rows

@@ -268,6 +268,27 @@ struct SlabRuns {
   }
 };
 
+// The same slab elements by tile (docs/ARCHITECTURE.md §26): record u of t is the SLAB_TILE_INTS ints
+//   [base, nch, stride, n0, k0, kq, fan_in, fan_out, w_off, b_off, nq, quad0]
+// of one wgrad output tile: chunk c of its row-major [nq * 64][kq * 64] fp32 tile starts at slab + base +
+// c * stride; dW[n][k] of the layer is flat element w_off + n * fan_in + k, its bias column k == fan_in is
+// b_off + n (offsets into the gathered slice).  A quad is four consecutive k of one (tile, n) — one
+// aligned 16-byte load per chunk; the tile owns quads [quad0, quad0 + rows * ceil(cols / 4)), rows =
+// min(nq * 64, fan_out - n0), cols = min(kq * 64, fan_in + 1 - k0): the padded rows and columns of a
+// tile are not read.  t null: the per-element form (src_off / src_meta).
+constexpr int SLAB_TILE_INTS = 12;
+constexpr int SLAB_TILES_MAX = 32;
+// chunks per batch of the streaming sum (common.h slab_sum4: two batches in flight, 2 x 6 x 4 VGPRs).  6 and
+// not 8: the tests want tiles of exactly one batch and of one batch + 1 chunks, and at their 34 64-row
+// blocks a tile has ceil(34 / k) chunks — 6 and 7 exist, 8 does not (tests/test_gather_stream.py)
+constexpr int SLAB_SUM_BATCH = 6;
+struct SlabTiles {
+  const int* t;
+  int n, nquads;
+};
+DEV_HOST_INLINE int slab_tile_rows(const int* e) { return e[10] * 64 < e[7] - e[3] ? e[10] * 64 : e[7] - e[3]; }
+DEV_HOST_INLINE int slab_tile_cols(const int* e) { return e[5] * 64 < e[6] + 1 - e[4] ? e[5] * 64 : e[6] + 1 - e[4]; }
+
 // reduce items per block of the gather kernels (common.h item_reduce)
 constexpr int ITEM_IPB = 32;
 inline __host__ __device__ int item_blocks(int nitems) { return (nitems + ITEM_IPB - 1) / ITEM_IPB; }
@@ -288,6 +309,7 @@ struct GatherArgs {
   SlabRuns runs;
   float scale;
   float* loss_out;      // [8]
+  SlabTiles tiles;      // (last) the runs' elements by tile: the streaming form; t null: per element
 };
 
 // One optimizer step over a flat range of n parameters (csrc/optim.hip): Adam, the global-norm clip
@@ -405,6 +427,8 @@ void launch_adam(const AdamArgs& a, hipStream_t s);
 // grad_gather + no-clip Adam in one launch: world size 1 only (no all-reduce between them); a.nblk
 // must exceed item_blocks(ga.nitems), and ungated it needs a.host_step >= 1
 void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipStream_t s);
+void set_gather_stream(int on);   // A/B switch: 0 runs the per-element form even with a tile table
+int gather_stream_on();
 // target_kl: the gate after a step (AdamArgs::gate); ra: the adaptive rate's block (null lr_state: none)
 void launch_kl_gate(const float* loss_sums, float* gate, float* state, float target_kl, const LrAdapt& ra,
                     hipStream_t s);

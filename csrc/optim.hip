@@ -341,7 +341,11 @@ __global__ __launch_bounds__(256) void adam_noclip_kernel(float* __restrict__ p,
 // narrow-layer weight gradients; item_reduce) and update their parameters; the rest grid-stride
 // over the slab elements of [i_lo, n) — the range may be one head's slice of the flat vectors
 // (runtime/engine_hip.py).  Every block leaves its sum of squares in norm_part.
-template <int DT, bool GATE = false>
+// STREAM (docs/ARCHITECTURE.md §26): the slab blocks grid-stride over the quads of the tile table
+// (kernels.h SlabTiles) instead — 16-byte chunk loads, double-buffered (common.h slab_sum4), the
+// element indices by arithmetic; every element is the same fixed-order sum, so p, m, v, g and the
+// images carry the bits of the per-element form.
+template <int DT, bool GATE = false, bool STREAM = false>
 __global__ __launch_bounds__(256) void gather_adam_kernel(
     const float* __restrict__ slab, const int* __restrict__ src_off, const int* __restrict__ src_meta,
     const float* __restrict__ part, int npblk, int npart, const int* __restrict__ red_col,
@@ -349,7 +353,7 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
     float* __restrict__ g, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, int n, float lr,
     float b1, float b2, float eps, float step_host, float* __restrict__ state, float* __restrict__ norm_part,
     typename Prec<DT>::T* __restrict__ wimg, const int* __restrict__ w_map, const int* __restrict__ wt_map,
-    const float* __restrict__ qmul, F8Shadow f8, KlGate<GATE> kg) {
+    const float* __restrict__ qmul, F8Shadow f8, KlGate<GATE> kg, SlabTiles tiles) {
   using P = Prec<DT>;
   __shared__ float red[256];
   const float step = GATE ? state[0] + 1.f : step_host;
@@ -412,20 +416,49 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
     return;
   }
   const int nb = gridDim.x - nrb;
-  for (int j = (blockIdx.x - nrb) * 256 + threadIdx.x; j < runs.total; j += nb * 256) {
-    // no data-dependent branch: every per-element load issues in one round trip, then the slab
-    // chunk loads (their addresses need src_off)
-    const int i = runs.flat(j);
-    const int mt = src_meta[i];
-    const int o = src_off[i];
-    const float mi = m[i], vi = v[i], pv = p[i];
-    const int wi = w_map[i], wti = wt_map[i];
-    const int nch = mt >> 5;
-    const size_t st = (size_t)(mt & 31) << 12;
-    const float s = slab_sum(slab + o, nch, st);
-    const float gi = s * scale;
-    ss = fmaf(gi, gi, ss);
-    update(i, gi, mi, vi, pv, wi, wti);
+  if constexpr (STREAM) {
+    __shared__ int tl[SLAB_TILES_MAX * SLAB_TILE_INTS];
+    slab_tiles_stage(tiles, tl);
+    for (int Q = (blockIdx.x - nrb) * 256 + threadIdx.x; Q < tiles.nquads; Q += nb * 256) {
+      const SlabQuad q = slab_quad(tl, tiles.n, Q, slab);
+      // the optimizer state of the quad's elements, issued before the chunk stream
+      float mi[4], vi[4], pv[4];
+      int wi[4], wti[4];
+#pragma unroll
+      for (int l = 0; l < 4; ++l) {
+        const int i = max(q.i[l], 0);   // (a lane past the bias column loads element 0 and drops it: no branch)
+        mi[l] = m[i];
+        vi[l] = v[i];
+        pv[l] = p[i];
+        wi[l] = w_map[i];
+        wti[l] = wt_map[i];
+      }
+      const float4 s = slab_sum4(q.src, q.nch, q.st4);
+      const float sl[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+      for (int l = 0; l < 4; ++l)
+        if (q.i[l] >= 0) {
+          const float gi = sl[l] * scale;
+          ss = fmaf(gi, gi, ss);
+          update(q.i[l], gi, mi[l], vi[l], pv[l], wi[l], wti[l]);
+        }
+    }
+  } else {
+    for (int j = (blockIdx.x - nrb) * 256 + threadIdx.x; j < runs.total; j += nb * 256) {
+      // no data-dependent branch: every per-element load issues in one round trip, then the slab
+      // chunk loads (their addresses need src_off)
+      const int i = runs.flat(j);
+      const int mt = src_meta[i];
+      const int o = src_off[i];
+      const float mi = m[i], vi = v[i], pv = p[i];
+      const int wi = w_map[i], wti = wt_map[i];
+      const int nch = mt >> 5;
+      const size_t st = (size_t)(mt & 31) << 12;
+      const float s = slab_sum(slab + o, nch, st);
+      const float gi = s * scale;
+      ss = fmaf(gi, gi, ss);
+      update(i, gi, mi, vi, pv, wi, wti);
+    }
   }
   red[threadIdx.x] = ss;
   __syncthreads();
@@ -687,6 +720,9 @@ extern "C" void launch_gae_rn(const float* rewards, const float* values, const f
 
 static int g_adam_fused = 1;   // A/B switch (set_adam_fused): 0 forces the sumsq + adam pair
 extern "C" void set_adam_fused(int on) { g_adam_fused = on; }
+static int g_gather_stream = 1;   // A/B switch (set_gather_stream): 0 keeps the gathers per element
+extern "C" void set_gather_stream(int on) { g_gather_stream = on; }
+extern "C" int gather_stream_on() { return g_gather_stream; }
 
 namespace {
 // f(integral_constant<int, DT>, KlGate<GATE>): the image's precision and, from a.gate, the gated
@@ -730,11 +766,15 @@ extern "C" void launch_gather_adam(const GatherArgs& ga, const AdamArgs& a, hipS
   dispatch_adam(a, [&](auto d, auto kg) {
     constexpr int DT = decltype(d)::value;
     constexpr bool GATE = std::is_same_v<decltype(kg), KlGate<true>>;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gather_adam_kernel<DT, GATE>), dim3(a.nblk), dim3(256), 0, s, ga.slab,
-                       ga.src_off, ga.src_meta, ga.part, ga.npblk, ga.npart, ga.red_col, ga.red_dst, ga.nitems,
-                       ga.runs, ga.scale, ga.loss_out, a.g, a.p, a.m, a.v, a.n, a.lr, a.b1, a.b2, a.eps,
-                       (float)a.host_step, a.state, a.norm_part, static_cast<typename Prec<DT>::T*>(a.wimg), a.w_map,
-                       a.wt_map, a.img_scale, a.f8, kg);
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(a.nblk), dim3(256), 0, s, ga.slab, ga.src_off, ga.src_meta, ga.part, ga.npblk,
+                         ga.npart, ga.red_col, ga.red_dst, ga.nitems, ga.runs, ga.scale, ga.loss_out, a.g, a.p, a.m,
+                         a.v, a.n, a.lr, a.b1, a.b2, a.eps, (float)a.host_step, a.state, a.norm_part,
+                         static_cast<typename Prec<DT>::T*>(a.wimg), a.w_map, a.wt_map, a.img_scale, a.f8, kg,
+                         ga.tiles);
+    };
+    if (ga.tiles.t != nullptr && g_gather_stream) go(gather_adam_kernel<DT, GATE, true>);
+    else go(gather_adam_kernel<DT, GATE, false>);
   });
   HIP_CHECK_LAUNCH();
 }

@@ -502,6 +502,8 @@ void launch_wgrad_lds(const WgradArgs& a, hipStream_t s) {
 // Blocks past them: grad[i] = scale * sum_{c < nch} slab[src_off[i] + c * stride] for the slab
 // elements i of `runs` (src_meta[i] = nch * 32 + stride / 4096, each tile has its own batch-chunk
 // count).  Fixed chunk order: deterministic; no float atomics anywhere.
+// STREAM: the same sums over the quads of the tile table (kernels.h SlabTiles, common.h slab_sum4).
+template <bool STREAM>
 __global__ __launch_bounds__(256) void grad_gather_kernel(const float* __restrict__ slab,
                                                           const int* __restrict__ src_off,
                                                           const int* __restrict__ src_meta,
@@ -509,7 +511,7 @@ __global__ __launch_bounds__(256) void grad_gather_kernel(const float* __restric
                                                           int nblk, int npart, const int* __restrict__ red_col,
                                                           const int* __restrict__ red_dst, int nitems,
                                                           float scale, float* __restrict__ grad, SlabRuns runs,
-                                                          float* __restrict__ loss_out) {
+                                                          float* __restrict__ loss_out, SlabTiles tiles) {
   const int nrb = item_blocks(nitems);
   if ((int)blockIdx.x < nrb) {
     __shared__ float red[256];
@@ -523,14 +525,27 @@ __global__ __launch_bounds__(256) void grad_gather_kernel(const float* __restric
     return;
   }
   const int nb = gridDim.x - nrb;
-  for (int j = (blockIdx.x - nrb) * 256 + threadIdx.x; j < runs.total; j += nb * 256) {
-    const int i = runs.flat(j);
-    const int mt = src_meta[i];
-    const int o = src_off[i];
-    const int nch = mt >> 5;
-    const size_t st = (size_t)(mt & 31) << 12;
-    const float s = slab_sum(slab + o, nch, st);
-    grad[i] = s * scale;
+  if constexpr (STREAM) {
+    __shared__ int tl[SLAB_TILES_MAX * SLAB_TILE_INTS];
+    slab_tiles_stage(tiles, tl);
+    for (int Q = (blockIdx.x - nrb) * 256 + threadIdx.x; Q < tiles.nquads; Q += nb * 256) {
+      const SlabQuad q = slab_quad(tl, tiles.n, Q, slab);
+      const float4 s = slab_sum4(q.src, q.nch, q.st4);
+      const float sl[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+      for (int l = 0; l < 4; ++l)
+        if (q.i[l] >= 0) grad[q.i[l]] = sl[l] * scale;
+    }
+  } else {
+    for (int j = (blockIdx.x - nrb) * 256 + threadIdx.x; j < runs.total; j += nb * 256) {
+      const int i = runs.flat(j);
+      const int mt = src_meta[i];
+      const int o = src_off[i];
+      const int nch = mt >> 5;
+      const size_t st = (size_t)(mt & 31) << 12;
+      const float s = slab_sum(slab + o, nch, st);
+      grad[i] = s * scale;
+    }
   }
 }
 
@@ -559,11 +574,16 @@ extern "C" void launch_wgrad(int dt, const WgradArgs& a, hipStream_t s) {
 }
 
 extern "C" void launch_grad_gather(const GatherArgs& ga, float* grad, hipStream_t s) {
-  int grid = (ga.runs.total + 255) / 256;
+  const bool stream = ga.tiles.t != nullptr && gather_stream_on();
+  int grid = ((stream ? ga.tiles.nquads : ga.runs.total) + 255) / 256;   // one quad / element per thread
   if (grid > 2048) grid = 2048;
   if (grid < 1) grid = 1;
   grid += item_blocks(ga.nitems);
-  hipLaunchKernelGGL(grad_gather_kernel, dim3(grid), dim3(256), 0, s, ga.slab, ga.src_off, ga.src_meta, ga.part,
-                     ga.npblk, ga.npart, ga.red_col, ga.red_dst, ga.nitems, ga.scale, grad, ga.runs, ga.loss_out);
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, ga.slab, ga.src_off, ga.src_meta, ga.part, ga.npblk,
+                       ga.npart, ga.red_col, ga.red_dst, ga.nitems, ga.scale, grad, ga.runs, ga.loss_out, ga.tiles);
+  };
+  if (stream) go(grad_gather_kernel<true>);
+  else go(grad_gather_kernel<false>);
   HIP_CHECK_LAUNCH();
 }

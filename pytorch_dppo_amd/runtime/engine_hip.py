@@ -330,14 +330,20 @@ class HipEngine(Engine):
         # (the fused gather + Adam launch takes one block per 32 reduce items first: with the fused
         # narrow / second-layer weight gradients there are tens of thousands of items)
         # (blocks of 32 items, csrc/kernels.h ITEM_IPB; blocks of 8 measured no faster, profiles/r6/ab_iter_phead_kb_vs_plain_ipb8_*.log)
-        n_whole = min(4096, max(n_whole, -(-len(self.items["joint"][0]) // 32) + (n + 255) // 256))
+        n_elem = min(4096, max(n_whole, -(-len(self.items["joint"][0]) // 32) + (n + 255) // 256))
+        # the streaming form (docs/ARCHITECTURE.md §26) takes one QUAD per thread behind the reduce blocks; n_elem
+        # stays the per-element form's grid (ext.set_gather_stream(0), scripts/ab_iter.py arm "elem")
+        fb = self.joint_bucket if self.heads else self.buckets[0]
+        fused_items = self.items["joint" if self.heads else "legacy"][0]
+        n_whole = min(4096, -(-len(fused_items) // 32) + (fb["nquads"] + 255) // 256) if self._tiles(fb) else n_elem
+        self.norm_n_elem = n_elem
         # per-head regions (fixed: every head launch writes each block of its region): policy
         # [0, np_), value [np_, np_ + nv_)
         (plo, phi), (vlo, vhi) = self.head_range
         np_ = min(4096, self.A + 8 + (phi - self.A + 255) // 256)
         nv_ = min(4096, 8 + (vhi - vlo + 255) // 256)
         self.norm_regions = [(0, np_), (np_, np_ + nv_)]
-        self.norm_part = torch.zeros(max(n_whole, np_ + nv_), **f32)
+        self.norm_part = torch.zeros(max(n_whole, n_elem, np_ + nv_), **f32)
         self.norm_n_whole = n_whole
         self._norm_n = n_whole       # entries the last Adam path wrote (metrics_pack sums them)
         # a value-head step not yet applied: ("work", all-reduce work, step, mean) on the
@@ -548,10 +554,22 @@ class HipEngine(Engine):
             has = sm > 0
             reach = so + ((sm >> 5) - 1).clamp(min=0) * ((sm & 31) << 12)
             assert bool((so[has] >= 0).all()) and int(reach[has].max()) < base, "wgrad gather plan exceeds its slab"
+            # the same elements by tile, for the gathers' streaming form (csrc/kernels.h SlabTiles):
+            # [base, nch, stride, n0, k0, kq, fan_in, fan_out, w_off, b_off, nq, quad0] per tile
+            rows, quad0 = [], 0
+            for t in tiles:
+                l = ls[t[0]]
+                tb, tn, size = tile_off[t]
+                rows.append([tb, tn, size, t[1], t[2], t[4], l.fan_in, l.fan_out, model.offsets[f"{l.name}.weight"][0],
+                             model.offsets[f"{l.name}.bias"][0], t[3], quad0])
+                quad0 += min(t[3] * 64, l.fan_out - t[1]) * (-(-min(t[4] * 64, l.fan_in + 1 - t[2]) // 4))
+            runs = self._slab_runs(sm, lo)
+            HipEngine._check_tile_table(rows, src, meta, runs)   # (by class: the plan also runs on a CPU stand-in)
             self.buckets.append({
                 "tasks_host": tasks_host, "tasks": tasks_host.to(self.device),
                 "slab": torch.zeros(base, device=self.device, dtype=torch.float32),
-                "lo": lo, "hi": hi, "partials": partials[bi], "runs": self._slab_runs(sm, lo)})
+                "lo": lo, "hi": hi, "partials": partials[bi], "runs": runs,
+                "tile_rows": rows, "nquads": quad0, "tiles": {}})
         src[src < 0] = 0  # reduce items (log_std, and with the per-head kernels mu / v)
         self.src_off = src.to(torch.int32).to(self.device)
         self.src_meta = meta.to(torch.int32).to(self.device)
@@ -602,6 +620,36 @@ class HipEngine(Engine):
                 start = None
         assert 2 <= len(runs) <= 8, "a gather takes 1-4 slab runs"
         return runs
+
+    @staticmethod
+    def _check_tile_table(rows: list, src: torch.Tensor, meta: torch.Tensor, runs: list) -> None:
+        """the tile table names exactly the runs' elements, each at the slab offset, chunk count and stride
+        that src_off / src_meta give it (the streaming gathers index the slab and the flat vectors by it
+        without a device check)"""
+        idx = []
+        for tb, tn, size, n0, k0, kq, fan_in, fan_out, woff, boff, nq, _ in rows:
+            nr, nc = min(nq * 64, fan_out - n0), min(kq * 64, fan_in + 1 - k0)
+            r = torch.arange(nr).repeat_interleave(nc)
+            c = torch.arange(nc).repeat(nr)
+            k = k0 + c
+            i = torch.where(k < fan_in, woff + (n0 + r) * fan_in + k, boff + n0 + r)
+            assert bool((src[i] == tb + r * (kq * 64) + c).all()) and bool((meta[i] == tn * 32 + size // 4096).all()), \
+                "tile table disagrees with src_off / src_meta"
+            idx.append(i)
+        idx = torch.cat(idx).sort().values
+        want = torch.cat([torch.arange(a, b) for a, b in zip(runs[0::2], runs[1::2])])
+        assert torch.equal(idx, want), "tile table does not cover the slab runs exactly"
+
+    def _tiles(self, b: Dict, lo: int = 0) -> tuple:
+        """bucket b's tile table as the gathers' trailing operands (device, CPU mirror), its flat offsets
+        relative to ``lo`` (a head's slice); (): the per-element form (more tiles than the kernels stage)"""
+        if len(b["tile_rows"]) > 32:         # csrc/kernels.h SLAB_TILES_MAX
+            return ()
+        if lo not in b["tiles"]:
+            host = torch.tensor([r[:8] + [r[8] - lo, r[9] - lo] + r[10:] for r in b["tile_rows"]],
+                                dtype=torch.int32).reshape(-1).contiguous()
+            b["tiles"][lo] = (host.to(self.device), host)
+        return b["tiles"][lo]
 
     def _reduce_items(self, model: ActorCritic) -> Dict[str, tuple]:
         """Reduce items of the gather launches: (partial-row column, destination) pairs, the
@@ -1645,10 +1693,10 @@ class HipEngine(Engine):
                 lo: int = 0, hi: Optional[int] = None) -> None:
         """the gather launch of bucket b into grad_flat; [lo, hi): into one head's slice of the flat vectors"""
         grad, runs = self.grad_flat, b["runs"]
-        if hi is not None:          # (red_dst indexes the slice: the runs rebased to it)
+        if hi is not None:          # (red_dst indexes the slice: the runs and the tile table rebased to it)
             src_off, src_meta, grad, runs = src_off[lo:hi], src_meta[lo:hi], grad[lo:hi], [r - lo for r in runs]
         self.ext.grad_gather(b["slab"], src_off, src_meta, part, npblk, part.shape[1], *items, 1.0 / self.mb, grad,
-                             self.loss_sums, runs)
+                             self.loss_sums, runs, *self._tiles(b, lo if hi is not None else 0))
 
     def _gather_adam(self, b: Dict, src_off: torch.Tensor, src_meta: torch.Tensor, part: torch.Tensor, npblk: int,
                      items) -> None:
@@ -1659,7 +1707,7 @@ class HipEngine(Engine):
                              1.0 / self.mb, self.loss_sums, self.grad_flat, self.model.flat.data, self.adam_m,
                              self.adam_v, float(self.lr), float(b1), float(b2), float(p.adam_eps), self._next_step(),
                              self.adam_state, self.norm_part[:self.norm_n_whole], self.wimg, self.w_map, self.wt_map,
-                             self.dt, self.no_q, *self._f8(), self._gate_arg, self._lr_arg)
+                             self.dt, self.no_q, *self._f8(), self._gate_arg, self._lr_arg, *self._tiles(b))
         self._stepped(self.norm_n_whole)
 
     def grad(self, idx: Optional[torch.Tensor], apply: bool = False) -> None:
@@ -1696,8 +1744,8 @@ class HipEngine(Engine):
         self._flush_value()
         if extra_grad:
             self.grad_flat.add_(extra_grad)
-        self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_whole], self.max_norm, self._next_step())
-        self._stepped(self.norm_n_whole)
+        self._adam(0, self.grad_flat.numel(), self.norm_part[:self.norm_n_elem], self.max_norm, self._next_step())
+        self._stepped(self.norm_n_elem)
 
     def pack_metrics(self, ep2: torch.Tensor, reduce=None) -> Optional[torch.Tensor]:
         """device f64[11] = [episode return sum, count | loss sums (8) | grad norm], written by ONE

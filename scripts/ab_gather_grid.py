@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Same-box A/B of the fused gather + Adam launch's grid: the engine's sizing (one slab element per
-thread) vs an override (e.g. the round-4 formula, A + 8 reduce blocks + one per 256 parameters),
+"""Same-box A/B of the fused gather + Adam launch's grid: the engine's sizing (one slab quad per
+thread behind the reduce blocks) vs an override (e.g. twice the slab blocks; the launch grid-strides),
 interleaved rounds of K deferred iterations in one process.  Diagnostics.
 
     python scripts/ab_gather_grid.py OVERRIDE_BLOCKS [rounds] [iters]

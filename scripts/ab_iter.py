@@ -56,10 +56,18 @@ def main():
                 variants[name] = native.load_variant(name)
             w.engine.ext = variants[name]
 
+    grids = (w.engine.norm_n_elem, w.engine.norm_n_whole)
+
+    def gather_form(stream):
+        ext.set_gather_stream(stream)
+        w.engine.norm_n_whole = grids[stream]
+
     arms = {
         "A": lambda: use_ext("A"), "B": lambda: use_ext("b"), "C": lambda: use_ext("c"),
         "x_cached": lambda: ext.set_x_stream(0), "x_stream": lambda: ext.set_x_stream(1),
         "s3w8": lambda: ext.set_s3_train_waves(8), "s3w4": lambda: ext.set_s3_train_waves(4),
+        # the gathers' streaming form vs the per-element form on its own grid (docs/ARCHITECTURE.md §26)
+        "stream": lambda: gather_form(1), "elem": lambda: gather_form(0),
         "pv": lambda: setattr(w.engine, "head_order", (0, 1)), "vp": lambda: setattr(w.engine, "head_order", (1, 0)),
     }
     for _ in range(2):

@@ -52,7 +52,7 @@ def build(dev, **flags):
 def whole_adam(eng, max_norm):
     """HipEngine.apply's launch over the whole vector, alone: the no-clip kernel, or the sumsq + adam pair"""
     n = eng.grad_flat.numel()
-    return lambda: eng._adam(0, n, eng.norm_part[:eng.norm_n_whole], max_norm, 0)
+    return lambda: eng._adam(0, n, eng.norm_part[:eng.norm_n_elem], max_norm, 0)
 
 
 def main():
