@@ -11,6 +11,8 @@
 //   (d) a = mu + sigma * eps, eps keyed (action key, e_base + r, step_key), one Box-Muller pair per
 //       two action dims; deterministic: a = mu, eps = 0
 //   (e) logp = sum_j(-0.5 eps_j^2 - log sigma_j) - 0.5 A log(2 pi)
+// ActArgs::dist 1 (a categorical head): (d), (e) are instead the Gumbel-max sample over the A logits, the one-hot
+// action row and logp = z_a - logsumexp(z) (policy_step.h categorical_row); mu receives the logits.
 // Every output is optional (null: skipped).  With none of actions / logp / mu the launch is
 // ROWS-ONLY: (a), (b) and the moments, no MLP (a rollout's bootstrap row).  Rows >= E of the last
 // tile are computed and never stored.  The kernel reads the policy image, log_std, the stats and
@@ -105,6 +107,22 @@ __global__ __launch_bounds__(NW * 64) void act_kernel(ActArgs a) {
   if (!mlp) return;
   // ---- (c) policy MLP ----
   ps.layers(wave, lane);
+  if (a.dist == 1) {
+    // ---- (d', e') categorical head: LPE lanes per row share its A logits (policy_step.h categorical_row) ----
+    constexpr int LPE = NTHR / ROWS;
+    const int r = tid / LPE, l = tid - r * LPE;
+    const float* z = L.t.mu + r * A;
+    const CatRow c = categorical_row<LPE>(z, A, l, L.kes[r], !det);
+    if (r < nvalid) {
+      const size_t o = (size_t)(e0 + r) * A;
+      for (int k = l; k < A; k += LPE) {
+        if (a.actions != nullptr) a.actions[o + k] = (k == c.a) ? 1.f : 0.f;   // the one-hot row
+        if (a.mu != nullptr) a.mu[o + k] = z[k];
+      }
+      if (l == 0 && a.logp != nullptr) a.logp[e0 + r] = c.logp;
+    }
+    return;
+  }
   // ---- (d) sample a = mu + sigma * eps ----
   sample_loop<ROWS, NTHR>(L.kes, A, tid, !det, [&](int r, int j, float eps) {
     const float mv = L.t.mu[r * A + j];

@@ -309,13 +309,14 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
 // logp [E], mu [E][A], x_out (E rows of d1 in the buffer precision, e.g. a slice of x_buf), mom
 // [ceil(E/16)][2][O] (overwritten with mom_init, else added to).  Every output is optional: an
 // empty tensor skips it; with none of actions / logp / mu the launch writes x_out / mom only.
-// ints: E,O,A,std_var,deterministic,mom_init; keys: action,e_base,step_key.
+// ints: E,O,A,std_var,deterministic,mom_init and optionally dist (0 Gaussian, the default; 1 categorical: actions gets
+// one-hot rows, mu the logits); keys: action,e_base,step_key.
 void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales,
                 torch::Tensor flat, torch::Tensor mean, torch::Tensor inv_std, torch::Tensor shift, torch::Tensor obs,
                 torch::Tensor actions, torch::Tensor logp, torch::Tensor mu, torch::Tensor x_out, torch::Tensor mom,
                 std::vector<int64_t> ints, std::vector<int64_t> keys, torch::Tensor qscale) {
   TORCH_CHECK(dt >= 0 && dt <= 3, "dt");
-  TORCH_CHECK(ints.size() == 6, "ints: E,O,A,std_var,deterministic,mom_init");
+  TORCH_CHECK(ints.size() == 6 || ints.size() == 7, "ints: E,O,A,std_var,deterministic,mom_init[,dist]");
   TORCH_CHECK(keys.size() == 3, "keys: action,e_base,step_key");
   TORCH_CHECK(scales.size() >= 3, "scales");
   Layout L = parse_layout(layout);
@@ -324,6 +325,9 @@ void policy_act(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std
   TORCH_CHECK(ints[1] >= 1 && ints[1] < (int64_t)1 << 20 && ints[2] >= 1 && ints[2] < (int64_t)1 << 20, "O / A");
   a.E = (int)ints[0]; a.O = (int)ints[1]; a.A = (int)ints[2];
   a.deterministic = ints[4] ? 1 : 0; a.mom_init = ints[5] ? 1 : 0;
+  a.dist = ints.size() == 7 ? (int)ints[6] : 0;
+  TORCH_CHECK(a.dist == 0 || a.dist == 1, "dist: 0 Gaussian, 1 categorical, got ", a.dist);
+  TORCH_CHECK(a.dist == 0 || a.A >= 2, "a categorical head has at least 2 actions, got ", a.A);
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout / O / A mismatch");
   for (int i = 0; i < 3; ++i)
     TORCH_CHECK(keys[i] >= 0 && keys[i] <= (int64_t)UINT32_MAX, "keys must be 32-bit, got ", keys[i]);
@@ -527,7 +531,7 @@ int64_t train_lds_bytes(int64_t dt, std::vector<int64_t> layout, int64_t A) {
 // share.  A binding passes its kernel's row tile ROWS, workgroup waves nw (the timestamp hook's extent), the
 // operand buffers' storage type and the parsed layout; the rest of this list leads its own.  tbufs: xT h1pT h2pT
 // h1vT h2vT g1pT g2pT g3pT g1vT g2vT g3vT, rows of ldT elements; idx empty: rows row0 .. row0 + M of x_buf; loss:
-// loss_kind (0 ppo, 1 dppo_ref), value_loss (0 mse, 1 clipped_half), std_var, first_step, clip, ent_coeff; part:
+// loss_kind (0 ppo, 1 dppo_ref, 2 ppo with a categorical head: mlp_train only), value_loss (0 mse, 1 clipped_half), std_var, first_step, clip, ent_coeff; part:
 // [ceil(M / ROWS)][npart] per-workgroup partial rows; xT_ready: xT holds the rows already; adv_norm: the fp32
 // [mean, inv, std, explained variance] block of csrc/advnorm.hip that the policy loss normalises adv by (empty: off).
 using Tensors = const std::vector<torch::Tensor>&;
@@ -564,6 +568,7 @@ MlpArgs train_args(int ROWS, int64_t nw, at::ScalarType operand, const Layout& L
   const int64_t nblk = Mpad / ROWS;
   a.part = fptr(part, "part", nblk * npart);
   a.npart = (int)npart;
+  TORCH_CHECK(loss[0] == 0 || loss[0] == 1 || loss[0] == 2, "loss_kind: 0 ppo, 1 dppo_ref, 2 categorical ppo");
   a.loss_kind = (int)loss[0]; a.value_loss = (int)loss[1]; a.std_var = (int)loss[2]; a.first_step = (int)loss[3];
   a.clip = (float)loss[4]; a.ent_coeff = (float)loss[5];
   // a precomputed xT is only valid for the identity row order from row 0
@@ -580,6 +585,9 @@ MlpArgs train_args(int ROWS, int64_t nw, at::ScalarType operand, const Layout& L
 
 // The three update bindings: train_args' parameters (from dt on; the pack P, deduced from it), then each kernel's own
 constexpr const char* HEADS_ONLY = "the per-head kernels cover split-bf16 / bf16 and the reference network only";
+constexpr const char* CATEGORICAL_TILE_ONLY =
+    "loss_kind 2 (a categorical head) runs on the tile kernel (mlp_train) only; the per-head and 32x32 policy kernels "
+    "have the Gaussian head";
 template <class F> struct TrainBind;
 template <class... P>
 struct TrainBind<MlpArgs (*)(int, int64_t, at::ScalarType, const Layout&, int64_t, int64_t, Tensors, P...)> {
@@ -611,6 +619,7 @@ struct TrainBind<MlpArgs (*)(int, int64_t, at::ScalarType, const Layout&, int64_
     const Q8Ring ring = q8 ? q8_ring(q8_amax, q8_step) : Q8Ring{};
     MlpArgs a = train_args(mlp_head_rows(), mlp_head_waves((int)head), q8 ? at::kByte : storage_type((int)dt), L, dt, A,
                            tbufs, p...);
+    TORCH_CHECK(a.loss_kind != 2, CATEGORICAL_TILE_ONLY);
     a.q8_acc = ring.acc; a.q8_rd = ring.rd; a.q8_clr = ring.clr;
     TORCH_CHECK(a.npart >= (head == 1 ? 8 : 8 + A), "npart too small");
     if (head == 0) TORCH_CHECK(part_dw >= 8 + A && part_dw + 32 * 128 <= a.npart, "part_dw: policy dW_mu block");
@@ -633,6 +642,7 @@ struct TrainBind<MlpArgs (*)(int, int64_t, at::ScalarType, const Layout&, int64_
     TORCH_CHECK((dt == 3 || dt == 1) && mlp_head_applies(s), HEADS_ONLY);
     TORCH_CHECK(phead_shape_ok(s), "phead: the policy head at bf16x3 / bf16");
     MlpArgs a = train_args(mlp_head_rows(), mlp_head_waves(0), storage_type((int)dt), L, dt, A, tbufs, p...);
+    TORCH_CHECK(a.loss_kind != 2, CATEGORICAL_TILE_ONLY);
     const int64_t ldT = a.ldT, npart = a.npart;
     TORCH_CHECK(npart >= 8 + A, "npart too small");
     TORCH_CHECK(part_dw >= 8 + A && part_dw + 32 * 128 <= npart, "part_dw: policy dW_mu block");

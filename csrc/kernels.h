@@ -126,6 +126,13 @@ struct ActArgs {
   void* x_out;         // [E][d1] buffer precision (XStore<DT>), row-major: e.g. a slice of x_buf
   float* mom;          // [nblk][2][O] sum(obs - shift), sum((obs - shift)^2) per 16-row workgroup (RolloutArgs::mom)
   int mom_init;        // != 0: mom is overwritten, 0: added to
+  // (last: every earlier member keeps its kernel-argument offset)
+  // 0: the Gaussian head above.  1: a categorical head over A actions (csrc/policy_step.h categorical_row) — the
+  // network's outputs are logits z; actions [E][A] gets the ONE-HOT row of the chosen action, the lowest k
+  // attaining max_k(z_k + g_k), g Gumbel noise keyed (key_action, e_base + row, step_key, k) (deterministic:
+  // g = 0, the arg-max); logp its log-softmax; mu the logits.  log_std must still be a valid [A] array: the launch's
+  // setup loads it into the sigma table, which the categorical step then never reads.
+  int dist;
 };
 
 // Episode bookkeeping of ONE step of a device-stepped tensor env (csrc/envstep.hip): what
@@ -190,7 +197,8 @@ struct MlpArgs {
   const float* v_old;     // [N]
   float* mu_prev;         // [N][A] dppo_ref: params of the previous step (read, then overwritten)
   float* v_prev;          // [N]
-  int loss_kind;          // 0 ppo, 1 dppo_ref
+  int loss_kind;          // 0 ppo, 1 dppo_ref, 2 ppo with a categorical head (the tile kernel only: actions
+                          // holds one-hot rows, the policy's outputs are logits, dL/dlog_std = 0)
   int value_loss;         // 0 mse, 1 clipped_half
   int std_var;
   float clip, ent_coeff;

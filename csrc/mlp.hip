@@ -3,7 +3,8 @@
 // mlp_value_kernel: V(x) for every buffer row (GAE input, train.py:87,109-112).
 // mlp_train_kernel: ONE launch per minibatch does, per ROWS-row tile, fully on-chip:
 //   gather rows by index (K10)  ->  policy head fwd (3 layers)  ->  value head fwd (3 layers)
-//   -> PPO loss (corrected ppo.py:148-167, or the reference DPPO loss train.py:142-161)
+//   -> PPO loss (corrected ppo.py:148-167 with the Gaussian head or, loss_kind 2, a categorical head over the
+//      layer's A logits; or the reference DPPO loss train.py:142-161)
 //      and its gradient w.r.t. mu / log_std / v  (K11 fwd)
 //   -> dgrad chain through mu/v and the two tanh layers of both heads (K11 bwd)
 // Activations never leave LDS except as the feature-major (transposed) operands of the
@@ -32,6 +33,13 @@ template <int G>
 DEV float group_sum(float x) {
 #pragma unroll
   for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, G);
+  return x;
+}
+
+template <int G>
+DEV float group_max(float x) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, G));
   return x;
 }
 
@@ -341,8 +349,8 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
     actv[q] = j < A ? a.actions[(size_t)lsrc * A + j] : 0.f;
   }
   const float l_adv = a.adv[lsrc], l_ret = a.ret[lsrc];
-  const float l_lpo = a.loss_kind == 0 ? a.logp_old[lsrc] : 0.f;
-  const float l_vold = a.loss_kind == 0 ? a.v_old[lsrc] : 0.f;
+  const float l_lpo = a.loss_kind != 1 ? a.logp_old[lsrc] : 0.f;
+  const float l_vold = a.loss_kind != 1 ? a.v_old[lsrc] : 0.f;
   __syncthreads();
   STAMP(6);
   layer_gemm<DT, ROWS, NW, EPI_LINEAR_F32, true>(H2p, ld2p, a.d_in[2], W + a.off_w[2], A, MU, A, a.scale[2], wave, lane,
@@ -403,6 +411,47 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
       }
       lent = group_sum<TPR>(lent);
       vold = l_vold;
+    } else if (a.loss_kind == 2) {
+      // ---- PPO with a categorical head: MU holds the A logits z, the action row o is one-hot ----
+      //   lse = m + log sum_k exp(z_k - m);  p_k = exp(z_k - lse);  logp = sum_k o_k z_k - lse
+      //   H = -sum_k p_k (z_k - lse)  (= lse - sum_k p_k z_k, without its cancellation at large logits)
+      //   dL/dz_k = dlogp (o_k - p_k) + ent_coeff p_k ((z_k - lse) + H);  dL/dlog_std = 0
+      // z_k - lse and never log p_k: p_k may underflow to 0.  A lane with no logit (j >= A) gives -inf to the
+      // max and 0 to the sums.
+      float m = -INFINITY;
+      for (int j = sub; j < A; j += TPR) m = fmaxf(m, MU[r * A + j]);
+      m = group_max<TPR>(m);
+      float se = 0.f, oz = 0.f;
+      for (int j = sub, q = 0; j < A; j += TPR, ++q) {
+        const float z = MU[r * A + j];
+        se += __expf(z - m);
+        oz += act_at(q, j) * z;
+      }
+      se = group_sum<TPR>(se);
+      oz = group_sum<TPR>(oz);
+      const float lse = m + __logf(se);
+      float H = 0.f;
+      for (int j = sub; j < A; j += TPR) {
+        const float lz = MU[r * A + j] - lse;
+        H -= __expf(lz) * lz;
+      }
+      H = group_sum<TPR>(H);
+      const float lr = (oz - lse) - l_lpo;
+      const float ratio = __expf(lr);
+      const float s1 = ratio * advv;
+      const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * advv;
+      lclip = -fminf(s1, s2);
+      const float dlogp = (s1 <= s2) ? -advv * ratio : 0.f;
+      kl = (ratio - 1.f) - lr;
+      cf = (fabsf(ratio - 1.f) > a.clip) ? 1.f : 0.f;
+      for (int j = sub, q = 0; j < A; j += TPR, ++q) {
+        const float lz = MU[r * A + j] - lse;
+        const float p = __expf(lz);
+        P::put(DMU, r * ldmu + j, valid ? dlogp * (act_at(q, j) - p) + a.ent_coeff * p * (lz + H) : 0.f);
+        DLS[r * A + j] = 0.f;
+      }
+      lent = -a.ent_coeff * H;
+      vold = l_vold;
     } else {
       // ---- reference DPPO loss (train.py:142-161): per-dim pdf ratio, variance convention ----
       const float invA = 1.f / (float)A;
@@ -453,7 +502,7 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
         else if (f2 > f1) dv = d2 * inr;
         else dv = 0.5f * d1 + 0.5f * d2 * inr;
       }
-      if (a.loss_kind != 0 && valid) a.v_prev[src] = v;
+      if (a.loss_kind == 1 && valid) a.v_prev[src] = v;
       P::put(DV, r * ldv, valid ? dv : 0.f);
       float* lrow = LOSS + r * NPART_FIXED;
       const float vm = valid ? 1.f : 0.f;

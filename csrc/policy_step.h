@@ -125,6 +125,60 @@ DEV void sample_loop(const uint32_t* kes, int A, int tid, bool sample, F&& body)
 DEV float logp_term(float eps, float log_sigma) { return -0.5f * eps * eps - log_sigma; }
 DEV float logp_const(int A) { return 0.5f * LOG_2PI_F * (float)A; }
 
+// ---- categorical head (ActArgs::dist 1): the tile's mu [rows][K] holds the K logits z of each row ----
+// Gumbel noise of action k: g = -log(-log u), u = uniform01(keyed(action key, env, step, k)) (utils/rng.py gumbel).
+// The accurate logf, not the hardware log2: the arg-max below is a comparison of z + g against the torch twin's.
+// The top bucket's u rounds to 1, so -log u is held at 2^-25 (g <= 17.33): finite for every hash.
+DEV float gumbel(uint32_t kes, uint32_t k) {
+  const float u = uniform01(hash_u32(kes ^ k));
+  return -logf(fmaxf(-logf(u), 0x1p-25f));
+}
+
+struct CatRow {
+  int a;        // the chosen action: the lowest k attaining max_k (z_k + g_k)
+  float logp;   // z_a - lse
+  float lse;    // m + log sum_k exp(z_k - m), m = max_k z_k
+};
+
+// One row's categorical step by its LPE lanes (consecutive in a wave, LPE a power of two <= 64; lane l takes
+// the logits l, l + LPE, ..): the max, the sum of exponentials and the arg-max of z + g as a (value, index) pair
+// that prefers the lower index on equal values, reduced by xor-shuffles; every lane gets the result.  A lane
+// with no logit (K < LPE) contributes -inf to the max and the arg-max and 0 to the sum.  sample false: g = 0
+// (the arg-max of the logits).  Every lane of the wave must call it (shuffles).
+template <int LPE>
+DEV CatRow categorical_row(const float* z, int K, int l, uint32_t kes, bool sample) {
+  float m = -INFINITY, bv = -INFINITY;
+  int bi = K;
+  for (int k = l; k < K; k += LPE) {
+    const float zk = z[k];
+    m = fmaxf(m, zk);
+    const float s = sample ? zk + gumbel(kes, (uint32_t)k) : zk;
+    if (s > bv) {   // ascending k: an equal later value does not replace
+      bv = s;
+      bi = k;
+    }
+  }
+#pragma unroll
+  for (int o = LPE / 2; o > 0; o >>= 1) {
+    m = fmaxf(m, __shfl_xor(m, o, LPE));
+    const float ov = __shfl_xor(bv, o, LPE);
+    const int oi = __shfl_xor(bi, o, LPE);
+    if (ov > bv || (ov == bv && oi < bi)) {
+      bv = ov;
+      bi = oi;
+    }
+  }
+  float se = 0.f;
+  for (int k = l; k < K; k += LPE) se += __expf(z[k] - m);
+#pragma unroll
+  for (int o = LPE / 2; o > 0; o >>= 1) se += __shfl_xor(se, o, LPE);
+  CatRow c;
+  c.a = bi < K ? bi : 0;   // (no comparison held: NaN logits; stay inside the row)
+  c.lse = m + __logf(se);
+  c.logp = z[c.a] - c.lse;
+  return c;
+}
+
 // Row-major buffer rows from the normalised LDS tile: one 16-byte store per 16 bytes of features
 // instead of ROWS element stores per feature (fire-and-forget, overlaps the MFMA layers).  bf16 /
 // fp32: the tile and the buffer share the element type; split-bf16: the 32-byte hi|lo group layout

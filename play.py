@@ -49,6 +49,8 @@ def main(argv=None):
         env = make_vec_env(None, 1, seed=seed, rank=0, max_episode_length=max_len, backend="gym", name=name)
     else:
         env = make_vec_env(get_spec(name), 1, seed=seed, rank=0, device="cpu", max_episode_length=max_len)
+    # a discrete env: the runner's action is the index the env's step takes (the distribution follows the env played)
+    runner.discrete = bool(getattr(getattr(env, "spec", None), "discrete", False))
     if (env.O, env.A) != (runner.O, runner.A):
         raise ValueError(f"env {name} has obs/act dims ({env.O}, {env.A}), the checkpoint's policy ({runner.O}, {runner.A})")
 

@@ -62,6 +62,12 @@ class GymVecEnv:
             except Exception:
                 pass
         self.E = int(num_envs)
+        space = self.envs[0].action_space
+        if not getattr(space, "shape", None):
+            # gym Discrete (shape ()): the adapter hands envs fp32 action vectors
+            raise ValueError(f"gym env {name!r} has the action space {space!r}: the gym backend steps Box action spaces "
+                             "only; discrete actions run as a registered tensor env (register_tensor_env(..., "
+                             "discrete=True), e.g. the builtin CartPole-v1)")
         self.O = int(self.envs[0].observation_space.shape[0])
         self.A = int(self.envs[0].action_space.shape[0])
         limit = getattr(getattr(self.envs[0], "spec", None), "max_episode_steps", None)

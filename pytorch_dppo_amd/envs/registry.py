@@ -8,7 +8,7 @@ env name resolves to
 * ``synthetic`` — an obs/act-dim-faithful synthetic locomotion task (CPU torch + HIP),
   used for every MuJoCo/Bullet name, or
 * ``tensor`` — a ``VecEnv`` subclass registered with :func:`register_tensor_env` (by this package:
-  ``CartPoleContinuous-v1``; by a user's ``--env-module``): torch ops on device tensors, stepped on
+  ``CartPoleContinuous-v1`` and the discrete-action ``CartPole-v1``; by a user's ``--env-module``): torch ops on device tensors, stepped on
   the device by the GPU engine (``HipEngine.rollout_stepped``); the cart-pole also has an in-kernel
   twin (kernel kind ``KIND_CARTPOLE``, ``--env-fused true``), or
 * ``gym`` — the real env through :mod:`pytorch_dppo_amd.envs.gym_adapter` with
@@ -39,6 +39,10 @@ class EnvSpec:
     act_dim: int
     kind: int
     time_limit: int       # gym TimeLimit max_episode_steps
+    # a discrete action space of act_dim actions: the policy's act_dim outputs are logits of a categorical
+    # distribution, the rollout buffer's action rows are one-hot, and the env's step / _dynamics receive the
+    # chosen index [E] int64 (docs/ARCHITECTURE.md §27).  Registered tensor envs only.
+    discrete: bool = False
 
 
 _SPECS = {}
@@ -69,18 +73,21 @@ def host_spec(name: str, obs_dim: int, act_dim: int, limit: int) -> EnvSpec:
     return EnvSpec(name, int(obs_dim), int(act_dim), KIND_HOST, int(limit))
 
 
-def register_tensor_env(name: str, cls, obs_dim: int, act_dim: int, time_limit: int) -> EnvSpec:
+def register_tensor_env(name: str, cls, obs_dim: int, act_dim: int, time_limit: int, discrete: bool = False) -> EnvSpec:
     """Register ``cls`` (a ``VecEnv`` subclass: ``state_dim``, ``_reset_state``, ``observe``,
     ``_dynamics`` as torch ops on its device tensors) under ``name``; ``make_vec_env`` builds it for
     the returned spec.  The names of the built-in table cannot be re-registered; registering the same
-    tensor env again (a module imported twice) replaces it."""
+    tensor env again (a module imported twice) replaces it.  ``discrete``: ``act_dim`` is the number of
+    actions (at least 2) and ``_dynamics(a, step_key)`` receives the chosen indices ``a [E] int64``."""
     if name in _SPECS and _SPECS[name].kind != KIND_TENSOR:
         raise ValueError(f"env {name!r} is a built-in entry and cannot be re-registered")
     if name.startswith("Synthetic-"):
         raise ValueError("the Synthetic-<obs>x<act> names are reserved")
     if int(obs_dim) < 1 or int(act_dim) < 1 or int(time_limit) < 1:
         raise ValueError("obs_dim, act_dim and time_limit must be positive")
-    spec = EnvSpec(name, int(obs_dim), int(act_dim), KIND_TENSOR, int(time_limit))
+    if discrete and int(act_dim) < 2:
+        raise ValueError(f"a discrete env has at least 2 actions (act_dim is their number), got act_dim={act_dim}")
+    spec = EnvSpec(name, int(obs_dim), int(act_dim), KIND_TENSOR, int(time_limit), bool(discrete))
     _SPECS[name] = spec
     _TENSOR_ENVS[name] = cls
     return spec

@@ -86,7 +86,10 @@ class VecEnv:
 
     @torch.no_grad()
     def step(self, actions: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict]:
-        a = actions.to(self.device, torch.float32).reshape(self.E, self.A)
+        if self.spec.discrete:    # the chosen action's index per env
+            a = actions.to(self.device, torch.int64).reshape(self.E)
+        else:
+            a = actions.to(self.device, torch.float32).reshape(self.E, self.A)
         k = self.t & rng.MASK32
         new_state, reward, terminal = self._dynamics(a, k)
         self.ep_len += 1
@@ -245,6 +248,21 @@ class CartPoleContinuousEnv(VecEnv):
 
 
 register_tensor_env("CartPoleContinuous-v1", CartPoleContinuousEnv, obs_dim=4, act_dim=1, time_limit=500)
+
+
+class CartPoleEnv(CartPoleContinuousEnv):
+    """gym CartPole-v1: the parent's physics, reset and termination under the two discrete pushes — action
+    index 1 is the force +10, index 0 the force -10.  A discrete tensor env (``CartPole-v1``, 2 actions): its
+    policy is categorical and ``_dynamics`` receives the indices ``a [E] int64``.  No in-kernel twin
+    (``kernel_kind`` None): the GPU engine steps it on the device (HipEngine.rollout_stepped)."""
+    kernel_kind = None
+
+    def _dynamics(self, a, step_key):
+        # +-1 is exact in fp32 and the parent's clamp keeps it: FORCE_MAG * (+-1), its own equations
+        return super()._dynamics((2.0 * a.to(torch.float32) - 1.0)[:, None], step_key)
+
+
+register_tensor_env("CartPole-v1", CartPoleEnv, obs_dim=4, act_dim=2, time_limit=500, discrete=True)
 
 
 def make_vec_env(spec: EnvSpec, num_envs: int, seed: int = 1, rank: int = 0, device="cpu",

@@ -28,17 +28,61 @@ def gaussian_logp(a: torch.Tensor, mu: torch.Tensor, log_std: torch.Tensor,
     return (-0.5 * z * z - 0.5 * LOG_2PI - log_sigma).sum(-1, keepdim=True)
 
 
+def _check_dist(dist: str) -> bool:
+    """True for a categorical head"""
+    if dist not in ("gaussian", "categorical"):
+        raise ValueError(f"dist must be gaussian|categorical, got {dist!r}")
+    return dist == "categorical"
+
+
+def categorical_logp(onehot: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+    """log-probability [B,1] of the one-hot rows ``onehot`` [B,K] under softmax(``logits``):
+    ``sum_k o_k z_k - lse``, ``lse = m + log sum_k exp(z_k - m)``, ``m = max_k z_k``."""
+    m = logits.max(-1, keepdim=True).values
+    lse = m + torch.log(torch.exp(logits - m).sum(-1, keepdim=True))
+    return (onehot * logits).sum(-1, keepdim=True) - lse
+
+
+def categorical_entropy(logits: torch.Tensor) -> torch.Tensor:
+    """entropy [B] of softmax(``logits``): ``H = lse - sum_k p_k z_k``, summed as ``-sum_k p_k (z_k - lse)``
+    (no cancellation between large logits; ``z_k - lse`` and never ``log p_k``: ``p_k`` may underflow to 0)."""
+    m = logits.max(-1, keepdim=True).values
+    lz = logits - (m + torch.log(torch.exp(logits - m).sum(-1, keepdim=True)))
+    return -(torch.exp(lz) * lz).sum(-1)
+
+
+def categorical_sample(logits: torch.Tensor, key_action: int, env_idx: torch.Tensor, step_key,
+                       deterministic: bool = False):
+    """Gumbel-max sample of softmax(``logits`` [E,K]), keyed like the Gaussian noise: ``a`` is the lowest ``k``
+    attaining ``max_k (z_k + g_k)``, ``g_k = rng.gumbel(key_action, env, step_key, k)``; ``deterministic``:
+    ``g = 0``, the arg-max of the logits.  Returns ``(index [E] int64, one-hot [E,K], logp [E])``."""
+    K = logits.shape[-1]
+    dims = torch.arange(K, device=logits.device, dtype=torch.int64)
+    s = logits
+    if not deterministic:
+        s = logits + rng.gumbel(key_action, env_idx.to(logits.device)[:, None], step_key, dims[None, :])
+    top = s == s.max(-1, keepdim=True).values
+    a = torch.where(top, dims[None, :], torch.full_like(dims, K)[None, :]).min(-1).values.clamp_max(K - 1)
+    onehot = torch.zeros_like(logits).scatter_(-1, a[:, None], 1.0)
+    return a, onehot, categorical_logp(onehot, logits).squeeze(-1)
+
+
 @torch.no_grad()
 def policy_act(model, stats, obs: torch.Tensor, key_action: int, env_idx: torch.Tensor, step_key: int,
-               convention: str = "std", deterministic: bool = False):
+               convention: str = "std", deterministic: bool = False, dist: str = "gaussian"):
     """One policy step for a batch of observations — the torch twin of ``csrc/act.hip``, the CPU
     path of ``runtime/policy.PolicyRunner`` and the GPU tests' oracle.  The expressions are
     ``TorchEngine.rollout``'s (normalise, policy forward, keyed noise, sample, log-prob), so a rollout
     step and this function agree bit for bit.  ``deterministic``: ``a = mu`` and ``eps = 0``.
 
-    Returns ``(action [E,A], logp [E], mu [E,A], x [E,O])``."""
+    Returns ``(action [E,A], logp [E], mu [E,A], x [E,O])``.  ``dist="categorical"``: the network's outputs are
+    the logits of ``A`` actions; returns ``(one-hot [E,A], logp [E], logits [E,A], x [E,O])`` of
+    ``categorical_sample`` (``log_std`` is unread)."""
     x = stats.normalize(obs)
     mu, log_std, _ = model(x)
+    if _check_dist(dist):
+        _, onehot, logp = categorical_sample(mu, key_action, env_idx, step_key, deterministic)
+        return onehot, logp, mu, x
     log_sigma = log_std if convention == "std" else 0.5 * log_std
     if deterministic:
         a = mu
@@ -137,17 +181,21 @@ def scale_rewards(rewards: torch.Tensor, scale: torch.Tensor, clip: float) -> to
 
 
 def ppo_loss(mu, log_std, v, actions, logp_old, adv, ret, v_old, *, clip: float,
-             ent_coeff: float, value_loss: str = "mse", convention: str = "std") -> Dict[str, torch.Tensor]:
+             ent_coeff: float, value_loss: str = "mse", convention: str = "std",
+             dist: str = "gaussian") -> Dict[str, torch.Tensor]:
     """Corrected PPO loss (ppo.py:148-167).
 
     ratio = exp(logp - logp_old) with logp_old recorded at rollout; clipped surrogate;
     value loss 'mse' = mean((v-R)^2) (ppo.py:164) or 'clipped_half' =
     0.5*mean(max((v-R)^2, (v_old+clip(v-v_old,+-eps)-R)^2)) (train.py:154-157);
     entropy bonus -ent_coeff * H (ppo.py:167).
+    ``dist="categorical"``: ``mu`` holds logits and ``actions`` one-hot rows; logp and the entropy (the batch mean
+    of the rows') are the categorical ones, ``log_std`` is unread, everything else is as for the Gaussian head.
     """
+    cat = _check_dist(dist)
     adv = adv.reshape(-1, 1)
     ret = ret.reshape(-1, 1)
-    logp = gaussian_logp(actions, mu, log_std, convention)
+    logp = categorical_logp(actions, mu) if cat else gaussian_logp(actions, mu, log_std, convention)
     ratio = torch.exp(logp - logp_old.reshape(-1, 1))
     surr1 = ratio * adv
     surr2 = ratio.clamp(1.0 - clip, 1.0 + clip) * adv
@@ -159,7 +207,7 @@ def ppo_loss(mu, log_std, v, actions, logp_old, adv, ret, v_old, *, clip: float,
         v_old = v_old.reshape(-1, 1)
         vc = v_old + (v - v_old).clamp(-clip, clip)
         loss_value = 0.5 * torch.max((v - ret) ** 2, (vc - ret) ** 2).mean()
-    ent = gaussian_entropy(log_std, convention).mean()
+    ent = (categorical_entropy(mu) if cat else gaussian_entropy(log_std, convention)).mean()
     loss_ent = -ent_coeff * ent
     with torch.no_grad():
         lr = (logp - logp_old.reshape(-1, 1))

@@ -2,6 +2,29 @@
 from __future__ import annotations
 
 
+def check_discrete(params, spec) -> bool:
+    """Whether ``spec`` (an ``EnvSpec`` or None) is a discrete-action env, i.e. the policy is categorical
+    (docs/ARCHITECTURE.md §27) — after refusing the settings a categorical policy is not built for, each with its
+    reason.  Both engines call it when they are built (and the worker before it builds a gym env)."""
+    if spec is None or not bool(getattr(spec, "discrete", False)):
+        return False
+    name = getattr(spec, "name", "?")
+    why = None
+    if params.loss == "dppo_ref":
+        why = "loss=dppo_ref is the reference's per-dimension Gaussian density ratio; a categorical policy has no such density (use loss=ppo)"
+    elif params.compat:
+        why = "compat reproduces the reference's Gaussian-policy quirks (the variance convention, the shared noise stream)"
+    elif params.dtype == "fp8":
+        why = "dtype=fp8 gains from the per-head e4m3 update path, which a categorical policy does not take (use fp32, bf16x3 or bf16)"
+    elif params.update_kernels == "heads":
+        why = "update_kernels=heads: the per-head and 32x32 policy kernels have the Gaussian head; the categorical loss runs on the tile kernel"
+    elif params.env_backend == "gym":
+        why = "env_backend=gym: the gym adapter steps Box action spaces only (gym Discrete spaces are not supported)"
+    if why is not None:
+        raise ValueError(f"env {name!r} has discrete actions (a categorical policy): {why}")
+    return True
+
+
 class Engine:
     """One engine owns the device-side state of one DPPO worker: the envs, the ``[T, E]`` rollout buffer, the flat
     parameters / gradient / Adam moments.  ``runtime/worker.py`` and ``runtime/launcher.py`` call exactly this:

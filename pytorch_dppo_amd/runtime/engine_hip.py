@@ -33,7 +33,7 @@ from ..ops import native, storage
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
 from ..utils.ret_stats import VAR_FLOOR as RET_VAR_FLOOR, RunningReturnStats
-from .engine import Engine
+from .engine import Engine, check_discrete
 from .engine_torch import load_ret_acc
 from .metrics_layout import NPART_FIXED, MetricsLayout
 
@@ -102,6 +102,10 @@ class HipEngine(Engine):
         self.env = env
         self.stats = stats
         self.device = device
+        # a discrete env (docs/ARCHITECTURE.md §27): the policy's A outputs are logits of a categorical distribution,
+        # `actions` holds one-hot rows, the env takes indices; act launches with dist 1, the update on the tile
+        # kernel with loss_kind 2 (the per-head and 32x32 policy kernels have the Gaussian head)
+        self.discrete = check_discrete(params, getattr(env, "spec", None))
         # dtype fp8 (BASELINE config 5): the forward GEMMs of the rollout policy and of the value
         # pass run on the OCP e4m3 MFMA (v_mfma_f32_16x16x32_fp8_fp8) with per-layer weight
         # scales; on the per-head path the value head's fc1 in the update and every weight-gradient
@@ -175,7 +179,7 @@ class HipEngine(Engine):
         # 65,536 rows: 4.2 vs 4.9 ms at bf16x3).  Params.update_kernels heads / tile force one path.
         mode = params.update_kernels
         ncu = (torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256)
-        self.heads = (mode != "tile" and bool(self.ext.head_applies(self.dt, self.layout, A))
+        self.heads = (mode != "tile" and not self.discrete and bool(self.ext.head_applies(self.dt, self.layout, A))
                       and (mode == "heads" or params.minibatch_rows() >= 128 * ncu))
         # fp8 mode on the per-head path: the wgrad operands (x^T, h1^T, g1^T, g2^T of both heads)
         # are e4m3 bytes with power-of-two scales — fixed for the activations, delayed per-tensor
@@ -330,7 +334,7 @@ class HipEngine(Engine):
         # (the fused gather + Adam launch takes one block per 32 reduce items first: with the fused
         # narrow / second-layer weight gradients there are tens of thousands of items)
         # (blocks of 32 items, csrc/kernels.h ITEM_IPB; blocks of 8 measured no faster, profiles/r6/ab_iter_phead_kb_vs_plain_ipb8_*.log)
-        n_elem = min(4096, max(n_whole, -(-len(self.items["joint"][0]) // 32) + (n + 255) // 256))
+        n_elem = min(4096, max(n_whole, -(-len(self.items.get("joint", self.items["legacy"])[0]) // 32) + (n + 255) // 256))
         # the streaming form (docs/ARCHITECTURE.md §26) takes one QUAD per thread behind the reduce blocks; n_elem
         # stays the per-element form's grid (ext.set_gather_stream(0), scripts/ab_iter.py arm "elem")
         fb = self.joint_bucket if self.heads else self.buckets[0]
@@ -401,6 +405,9 @@ class HipEngine(Engine):
         elif bool(getattr(params, "env_fused", False)):
             self.kernel_kind = kernel_kind_of(env)
         self.stepped_env = not self.host_env and self.kernel_kind is None
+        if self.discrete and not self.stepped_env:
+            raise ValueError(f"env {env.spec.name!r} has discrete actions: the rollout and evaluation kernels have the "
+                             "Gaussian head, a discrete env runs device-stepped (not with env_fused)")
         # bootstrap_time_limit: which steps ended by the step limit alone (trunc, like dones), the
         # normalised observation each reached before its reset (x_fin [K][E][d0] in x_buf's storage:
         # slot t // limit, an env's truncations being >= limit steps apart) and its value.  Transient:
@@ -679,9 +686,11 @@ class HipEngine(Engine):
                 for k in range(l.fan_in):
                     add(kind, dw + j * stride + k, wo - base + j * l.fan_in + k)
                 add(kind, dw + j * stride + l.fan_in, bo - base + j)
+        # (the head kernels' dW_mu block holds 32 output rows: a wider action head — 40 logits of a categorical
+        # policy — never takes them, and has no per-head items)
         for kind, dwp, dwv, vbase in (("policy", self.part_dw[0], None, None),
                                       ("value", None, self.part_dw[1], vlo),
-                                      ("joint", self.part_dw_joint[0], self.part_dw_joint[1], 0)):
+                                      ("joint", self.part_dw_joint[0], self.part_dw_joint[1], 0)) if A <= 32 else ():
             if dwp is not None:
                 for q in (0, 2, 3, 4, 5, 6, 7):
                     add(kind, q, -1 - q)
@@ -695,6 +704,8 @@ class HipEngine(Engine):
                 narrow(kind, "v", dwv, vbase)
         out = {}
         for kind in cols:
+            if not cols[kind]:
+                continue
             c = torch.tensor(cols[kind], dtype=torch.int32)
             d = torch.tensor(dsts[kind], dtype=torch.int32)
             # the gather kernels index part rows and flat slices by these without a device check
@@ -1082,7 +1093,8 @@ class HipEngine(Engine):
             env.state = env.state.contiguous()
 
         def advance(t, rows, a, k):
-            new_state, reward, terminal = env._dynamics(a, k)
+            # (a discrete env: the index of the one-hot row, on the device)
+            new_state, reward, terminal = env._dynamics(a.argmax(1) if self.discrete else a, k)
             reset_state = env._reset_state(k)
             # (.to / .contiguous: no-ops for an env that returns fp32 / bool contiguous tensors)
             adv_args = (reward.to(torch.float32).contiguous(), terminal.to(torch.bool).contiguous(),
@@ -1127,7 +1139,7 @@ class HipEngine(Engine):
         def act_fn(obs, step_key):
             self._launch_act(obs.to(torch.float32).contiguous(), step_key, deterministic, 0, key_action, self.stats,
                              self.stats.shift(), a, none, none, self.empty_x, none, False)
-            return a
+            return a.argmax(1) if self.discrete else a
         return evaluate_batch(self.model, self.stats, env, E, p.seed, p.max_episode_length, p.std_convention,
                               deterministic, act_fn=act_fn, early_exit=False)
 
@@ -1252,7 +1264,8 @@ class HipEngine(Engine):
                     norm: RunningObsStats, shift: torch.Tensor, actions: torch.Tensor, logp: torch.Tensor,
                     mu: torch.Tensor, x_out: torch.Tensor, mom: torch.Tensor, mom_init: bool) -> None:
         """one csrc/act.hip launch on the current stream (an empty tensor skips that output)"""
-        ints = [obs.shape[0], self.O, self.A, self.std_var, 1 if deterministic else 0, 1 if mom_init else 0]
+        ints = [obs.shape[0], self.O, self.A, self.std_var, 1 if deterministic else 0, 1 if mom_init else 0,
+                1 if self.discrete else 0]
         keys = [key_action & 0xFFFFFFFF, e_base & 0xFFFFFFFF, step_key & 0xFFFFFFFF]
         self.ext.policy_act(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data, norm.mean_f32,
                             norm.inv_std_f32, shift, obs, actions, logp, mu, x_out, mom, ints, keys, self.qscale)
@@ -1264,7 +1277,7 @@ class HipEngine(Engine):
         """One policy step for caller-supplied observations (csrc/act.hip): ``obs`` fp32 ``[E', O]``
         on the device, any ``E' >= 1`` (not tied to the engine's env count).  ONE launch on the
         current stream, no host sync; returns the device tensors ``(action [E',A], logp [E'],
-        mu [E',A])`` this engine owns (rewritten by the next call for the same ``E'``).  The noise
+        mu [E',A])`` (a discrete env: the one-hot rows, their log-probability, the logits) this engine owns (rewritten by the next call for the same ``E'``).  The noise
         of row r is keyed (``key_action``, ``e_base + r``, ``step_key``); ``step_key`` defaults to
         the env's step counter, ``key_action`` to the engine's action stream.  ``x_out``: ``E'``
         rows of ``d0`` in the buffer's storage precision (e.g. a slice of ``x_buf``) receive the
@@ -1600,7 +1613,7 @@ class HipEngine(Engine):
         first_step, clip, ent_coeff]; ldT; the partial rows and their width; xt_ready; the advantage block of
         adv_norm_scope global | minibatch (empty: off)"""
         p = self.p
-        loss = [float(p.loss != "ppo"), float(p.value_loss != "mse"), float(self.std_var), float(first),
+        loss = [2.0 if self.discrete else float(p.loss != "ppo"), float(p.value_loss != "mse"), float(self.std_var), float(first),
                 float(p.clip), float(p.ent_coeff)]
         return (self.dt, self.A, self.tbufs, self.layout, self.x_buf, idx_t, 0, self.mb, self.wimg, self.scales,
                 self.model.flat.data, self.log_std_old, self.actions, self.logp, self.adv, self.ret, self.values_buf,

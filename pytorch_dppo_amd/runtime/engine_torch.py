@@ -24,7 +24,7 @@ from ..ops import oracle
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
 from ..utils.ret_stats import RunningReturnStats
-from .engine import Engine
+from .engine import Engine, check_discrete
 
 
 class TorchEngine(Engine):
@@ -37,6 +37,9 @@ class TorchEngine(Engine):
         self.env = env
         self.stats = stats
         self.device = device
+        # a discrete env: the policy's A outputs are logits, `actions` holds one-hot rows, the env takes indices
+        self.discrete = check_discrete(params, getattr(env, "spec", None))
+        self.dist = "categorical" if self.discrete else "gaussian"
         T, E = params.rollout_len, env.E
         O, A = env.O, env.A
         self.T, self.E, self.O, self.A = T, E, O, A
@@ -125,10 +128,13 @@ class TorchEngine(Engine):
                 norm_stats.observes(raw)
             x = norm_stats.normalize(raw)
             mu, _, _ = self.model(x)
-            eps = rng.gauss(self.key_action, eidx[:, None], self.env.t, dims[None, :])
-            a = mu + sigma * eps
-            logp = (-0.5 * eps * eps - 0.5 * oracle.LOG_2PI - log_sigma).sum(-1)
-            obs, r, done, info = self.env.step(a)
+            if self.discrete:
+                ai, a, logp = oracle.categorical_sample(mu, self.key_action, eidx, self.env.t)
+            else:
+                eps = rng.gauss(self.key_action, eidx[:, None], self.env.t, dims[None, :])
+                ai = a = mu + sigma * eps
+                logp = (-0.5 * eps * eps - 0.5 * oracle.LOG_2PI - log_sigma).sum(-1)
+            obs, r, done, info = self.env.step(ai)
             if p.reward_clip > 0:
                 r = r.clamp(-p.reward_clip, p.reward_clip)
             self.x[t] = x
@@ -258,7 +264,7 @@ class TorchEngine(Engine):
             v_old = self.values_buf[:self.T].reshape(N)[idx]
             out = oracle.ppo_loss(mu, log_std, v, a, logp_old, adv, ret, v_old, clip=p.clip,
                                   ent_coeff=p.ent_coeff, value_loss=p.value_loss,
-                                  convention=p.std_convention)
+                                  convention=p.std_convention, dist=self.dist)
         else:
             with torch.no_grad():
                 mu_o, ls_o, v_o = _forward_with(self.model, self.flat_old, x)

@@ -24,8 +24,15 @@ import torch
 
 from ..envs import get_spec, host_spec, import_env_module, make_vec_env
 from ..models.actor_critic import ActorCritic
+from ..ops import oracle
 from ..utils import rng
 from ..utils.obs_stats import RunningObsStats
+
+
+def is_discrete(env_or_spec) -> bool:
+    """a discrete-action env (EnvSpec.discrete): a categorical policy, the env takes action indices"""
+    spec = getattr(env_or_spec, "spec", env_or_spec)
+    return bool(getattr(spec, "discrete", False))
 
 
 def run_episode(model: ActorCritic, stats: RunningObsStats, env, key_action: int,
@@ -37,7 +44,9 @@ def run_episode(model: ActorCritic, stats: RunningObsStats, env, key_action: int
         while length < max_steps:
             x = stats.normalize(obs)
             mu, log_std, _ = model(x)
-            if deterministic:
+            if is_discrete(env):
+                a = oracle.categorical_sample(mu, key_action, env.env_idx, env.t, deterministic)[0]
+            elif deterministic:
                 a = mu
             else:
                 sig = torch.exp(log_std if convention == "std" else 0.5 * log_std)
@@ -77,7 +86,8 @@ def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_
     here).  Returns ``(ret fp32 [E], len int32 [E])``: the sum of the unclipped rewards, added in
     step order in fp32 as ``VecEnv.ep_ret`` does, and the episode length.
 
-    ``act_fn(obs, step_key) -> actions [E, A]``: the policy step, in place of the torch one below
+    A discrete env (``EnvSpec.discrete``) takes ``oracle.categorical_sample`` of the logits and is stepped with the
+    indices.  ``act_fn(obs, step_key) -> actions [E, A]`` (a discrete env: the indices ``[E]``): the policy step, in place of the torch one below
     (``model``, ``stats``, ``convention`` and ``deterministic`` are then its business;
     HipEngine.evaluate passes one ``csrc/act.hip`` launch).  ``early_exit=False`` drops the
     ``active.any()`` break — the loop's only host sync — and runs all ``limit`` steps; the masked
@@ -100,13 +110,16 @@ def evaluate_batch(model: ActorCritic, stats: RunningObsStats, spec_or_env, num_
     length = torch.zeros(E, dtype=torch.int32, device=env.device)
     active = torch.ones(E, dtype=torch.bool, device=env.device)
     dims = torch.arange(env.A, dtype=torch.int64, device=env.device)
+    discrete = is_discrete(env)
     for _ in range(env.limit):      # every first episode ends by step limit - 1
         if act_fn is not None:
             a = act_fn(obs, env.t)
         else:
             x = stats.normalize(obs.to(dev))
             mu, log_std, _ = model(x)
-            if deterministic:
+            if discrete:
+                a = oracle.categorical_sample(mu, key_action, env.env_idx.to(dev), env.t, deterministic)[0]
+            elif deterministic:
                 a = mu
             else:
                 sig = torch.exp(log_std if convention == "std" else 0.5 * log_std)

@@ -31,6 +31,7 @@ from ..models.actor_critic import ActorCritic
 from ..parallel.dist import DistContext
 from ..utils.metrics import MetricsLogger, PhaseTimer
 from ..utils.obs_stats import RunningObsStats
+from .engine import check_discrete
 from .metrics_layout import MetricsLayout
 
 
@@ -49,6 +50,10 @@ class DPPOWorker:
         self.device = ctx.device
         import_env_module(params.env_module)    # a user's register_tensor_env calls (spawned ranks too)
         if params.env_backend == "gym":
+            try:    # a registered discrete env by this name: refused with its reason before gym is asked for it
+                check_discrete(params, get_spec(params.env_name))
+            except KeyError:
+                pass
             # real gym envs (main.py:45 / train.py:48): dims from the env's own spaces
             self.env = make_vec_env(None, params.num_envs, seed=params.seed, rank=ctx.rank,
                                     max_episode_length=params.max_episode_length, backend="gym",

@@ -66,6 +66,17 @@ def uniform01(h: torch.Tensor) -> torch.Tensor:
     return ((h >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
 
 
+GUMBEL_E_MIN = 2.0 ** -25
+
+
+def gumbel(base: int, env: torch.Tensor, step, dim: torch.Tensor) -> torch.Tensor:
+    """Standard Gumbel noise ``g = -log(-log u)``, ``u = uniform01(keyed(base, env, step, dim))``, in fp32
+    (a categorical policy's Gumbel-max sample; ``csrc/policy_step.h`` gumbel).  The top bucket's ``u``
+    rounds to 1 in fp32, so ``-log u`` is held at ``2^-25``: finite for every hash, ``g`` in [-2.86, 17.33]."""
+    u = uniform01(keyed(base, env, step, dim.to(torch.int64)))
+    return -torch.log(torch.clamp_min(-torch.log(u), GUMBEL_E_MIN))
+
+
 def gauss(base: int, env: torch.Tensor, step, dim: torch.Tensor) -> torch.Tensor:
     """Standard normal by Box-Muller; dims 2p and 2p+1 share one uniform pair p (keys 2p, 2p+1)
     and take its cosine and sine branch respectively, so a kernel draws two normals per pair."""
