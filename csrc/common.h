@@ -20,6 +20,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 #define DEV __device__ __forceinline__
+constexpr float LOG_2PI_F = 1.8378770664093453f;   // log(2 pi): the Gaussian log-prob and entropy
 // MlpArgs::adv_norm at the update kernels' advantage load: a' = fl32(fl32(a - mean) * inv), two separately
 // rounded fp32 operations (ops/oracle.adv_apply); the product carries no contract flag, so no later add fuses it
 DEV float adv_norm_apply(float a, float mean, float inv) {

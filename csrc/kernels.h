@@ -170,6 +170,13 @@ struct EnvStepArgs {
 constexpr int Q8_SUB = 64, Q8_LINE = 32;
 constexpr int Q8_SLOT = 4 * Q8_SUB * Q8_LINE;   // dwords per ring slot
 
+// The loss row: the first LS_FIXED columns of a partial row (MlpArgs::part) and the loss sums the
+// gather kernels make of them — sums over the rows of the policy loss, the value loss, the entropy
+// bonus, the approximate KL and the clip flag, then the row count; the rest stay 0.  The same order
+// by name: runtime/metrics_layout.py LOSS_SLOTS.
+enum LossSlot { LS_CLIP = 0, LS_VALUE, LS_ENT, LS_KL, LS_CLIPFRAC, LS_COUNT, LS_FIXED = 8 };
+static_assert(LS_COUNT + 2 == LS_FIXED - 1, "the kernels zero the two unused slots LS_COUNT + 1 and LS_FIXED - 1");
+
 struct MlpArgs {
   // input rows: x_buf row-major [*][d1]; row m of this call reads x_buf[idx ? idx[m] : row0 + m]
   const void* x_buf;
@@ -212,7 +219,7 @@ struct MlpArgs {
   int xT_ready;           // 1: xT already holds this call's rows (full-batch: the rollout wrote it)
   int x_stream;           // 1: non-temporal observation-row loads (A/B knob; 0 default: cached)
   int64_t x_bytes;        // bytes of x_buf (kernels with 32-bit buffer offsets refuse >= 2 GiB)
-  float* part;            // [nblk][NPART] per-workgroup partial sums (loss terms, dlog_std)
+  float* part;            // [nblk][NPART] per-workgroup partial sums (loss terms: LossSlot below, dlog_std)
   int npart;
   int part_dw;            // per-head kernels: column of the fused narrow-layer weight gradient in a
                           // partial row (policy: dW_mu [32][128], value: dW_v [128]; bias = column 100)

@@ -12,12 +12,10 @@
 // The dgrad outputs overwrite the forward activations in place: dpre = (dY W) * (1 - h^2)
 // reads h and writes dpre at the same (row, col) from the same lane.
 #include "kernels.h"
+#include "loss_core.h"
 #include "mlp_core.h"
 
 namespace {
-
-constexpr float LOG_2PI_F = 1.8378770664093453f;
-constexpr int NPART_FIXED = 8;
 
 // phase timeline (diagnostics): lane 0 of each wave of every tstamp_every-th workgroup records
 // the shader clock at phase boundaries; one scalar branch per boundary when off
@@ -263,7 +261,7 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
   float* MU = cv.take<float>(ROWS * A);
   float* V = cv.take<float>(ROWS);
   float* DLS = cv.take<float>(ROWS * A);
-  float* LOSS = cv.take<float>(ROWS * NPART_FIXED);
+  float* LOSS = cv.take<float>(ROWS * LS_FIXED);
 
   const T* W = reinterpret_cast<const T*>(a.W);
   STAMP(0);
@@ -389,25 +387,21 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
       for (int j = sub, q = 0; j < A; j += TPR, ++q) {
         const float lsig = cvar * a.log_std[j];
         const float z = (act_at(q, j) - MU[r * A + j]) * __expf(-lsig);
-        logp += -0.5f * z * z - 0.5f * LOG_2PI_F - lsig;
+        logp += gauss_logp_dim(z, lsig);
       }
       logp = group_sum<TPR>(logp);
-      const float lr = logp - l_lpo;
-      const float ratio = __expf(lr);
-      const float s1 = ratio * advv;
-      const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * advv;
-      lclip = -fminf(s1, s2);
-      const float dlogp = (s1 <= s2) ? -advv * ratio : 0.f;
-      kl = (ratio - 1.f) - lr;
-      cf = (fabsf(ratio - 1.f) > a.clip) ? 1.f : 0.f;
+      const Surrogate sg = ppo_surrogate(logp - l_lpo, advv, a.clip);
+      lclip = sg.loss;
+      kl = sg.kl;
+      cf = sg.clipped;
       for (int j = sub, q = 0; j < A; j += TPR, ++q) {
         const float lsig = cvar * a.log_std[j];
         const float isig = __expf(-lsig);
         const float z = (act_at(q, j) - MU[r * A + j]) * isig;
-        P::put(DMU, r * ldmu + j, valid ? dlogp * z * isig : 0.f);
-        // d/dlog_std: logp term + entropy bonus (-ent_coeff * sum_j log sigma_j)
-        DLS[r * A + j] = valid ? (dlogp * (z * z - 1.f) - a.ent_coeff) * cvar : 0.f;
-        lent += -a.ent_coeff * (0.5f + 0.5f * LOG_2PI_F + lsig);
+        const GaussGrad g = gauss_grad_dim(z, isig, sg.dlogp, a.ent_coeff, cvar);
+        P::put(DMU, r * ldmu + j, valid ? g.dmu : 0.f);
+        DLS[r * A + j] = valid ? g.dls : 0.f;
+        lent += gauss_ent_dim(lsig, a.ent_coeff);
       }
       lent = group_sum<TPR>(lent);
       vold = l_vold;
@@ -436,18 +430,14 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
         H -= __expf(lz) * lz;
       }
       H = group_sum<TPR>(H);
-      const float lr = (oz - lse) - l_lpo;
-      const float ratio = __expf(lr);
-      const float s1 = ratio * advv;
-      const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * advv;
-      lclip = -fminf(s1, s2);
-      const float dlogp = (s1 <= s2) ? -advv * ratio : 0.f;
-      kl = (ratio - 1.f) - lr;
-      cf = (fabsf(ratio - 1.f) > a.clip) ? 1.f : 0.f;
+      const Surrogate sg = ppo_surrogate((oz - lse) - l_lpo, advv, a.clip);
+      lclip = sg.loss;
+      kl = sg.kl;
+      cf = sg.clipped;
       for (int j = sub, q = 0; j < A; j += TPR, ++q) {
         const float lz = MU[r * A + j] - lse;
         const float p = __expf(lz);
-        P::put(DMU, r * ldmu + j, valid ? dlogp * (act_at(q, j) - p) + a.ent_coeff * p * (lz + H) : 0.f);
+        P::put(DMU, r * ldmu + j, valid ? cat_grad_dim(act_at(q, j), p, lz, H, sg.dlogp, a.ent_coeff) : 0.f);
         DLS[r * A + j] = 0.f;
       }
       lent = -a.ent_coeff * H;
@@ -462,20 +452,13 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
         const float mu_o = first ? mu : a.mu_prev[(size_t)src * A + j];
         const float var_o = first ? var : __expf(a.log_std_old[j]);
         const float x = act_at(q, j);
-        const float p = __expf(-(x - mu) * (x - mu) / (2.f * var)) * rsqrtf(2.f * var * 3.14159265358979f);
-        const float po = __expf(-(x - mu_o) * (x - mu_o) / (2.f * var_o)) * rsqrtf(2.f * var_o * 3.14159265358979f);
-        const float ratio = p / (1e-10f + po);
-        const float s1 = ratio * advv;
-        const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * advv;
-        lclip += -fminf(s1, s2) * invA;
-        const float dratio = (s1 <= s2) ? -advv * invA : 0.f;
-        float dp = dratio / (1e-10f + po);
-        const float lg = logf(p + 1e-5f);
-        lent += -a.ent_coeff * p * lg * invA;
-        dp += -a.ent_coeff * invA * (lg + p / (p + 1e-5f));
-        P::put(DMU, r * ldmu + j, valid ? dp * p * (x - mu) / var : 0.f);
-        DLS[r * A + j] = valid ? dp * p * ((x - mu) * (x - mu) / (2.f * var) - 0.5f) : 0.f;
-        cf += (fabsf(ratio - 1.f) > a.clip) ? invA : 0.f;
+        const RefDim t = dppo_ref_dim(x, mu, var, mu_o, var_o, advv, a.clip, a.ent_coeff, invA, lclip, lent);
+        lclip = t.lclip;
+        lent = t.lent;
+        const float dp = dppo_ref_dp(t, advv, a.ent_coeff, invA);
+        P::put(DMU, r * ldmu + j, valid ? dppo_ref_dmu(dp, t.p, x, mu, var) : 0.f);
+        DLS[r * A + j] = valid ? dppo_ref_dls(dp, t.p, x, mu, var) : 0.f;
+        cf += dppo_ref_cf(t, a.clip, invA);
         if (valid) a.mu_prev[(size_t)src * A + j] = mu;   // train.py:164 model_old <- model
       }
       lclip = group_sum<TPR>(lclip);
@@ -484,30 +467,17 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
       vold = first ? v : a.v_prev[src];
     }
     if (sub == 0) {
-      const float retv = l_ret;
+      const float d1 = v - l_ret;
       float dv, lv;
-      if (a.value_loss == 0) {
-        const float d = v - retv;
-        lv = d * d;
-        dv = 2.f * d;
-      } else {
-        const float d1 = v - retv;
-        const float dd = v - vold;
-        const float vc = vold + fminf(fmaxf(dd, -a.clip), a.clip);
-        const float d2 = vc - retv;
-        const float f1 = d1 * d1, f2 = d2 * d2;
-        const float inr = (dd >= -a.clip && dd <= a.clip) ? 1.f : 0.f;
-        lv = 0.5f * fmaxf(f1, f2);
-        if (f1 > f2) dv = d1;
-        else if (f2 > f1) dv = d2 * inr;
-        else dv = 0.5f * d1 + 0.5f * d2 * inr;
-      }
+      if (a.value_loss == 0) value_mse(d1, lv, dv);
+      else value_clipped_half(d1, v, l_ret, vold, a.clip, lv, dv);
       if (a.loss_kind == 1 && valid) a.v_prev[src] = v;
       P::put(DV, r * ldv, valid ? dv : 0.f);
-      float* lrow = LOSS + r * NPART_FIXED;
+      float* lrow = LOSS + r * LS_FIXED;
       const float vm = valid ? 1.f : 0.f;
-      lrow[0] = lclip * vm; lrow[1] = lv * vm; lrow[2] = lent * vm; lrow[3] = kl * vm; lrow[4] = cf * vm;
-      lrow[5] = vm; lrow[6] = 0.f; lrow[7] = 0.f;
+      lrow[LS_CLIP] = lclip * vm; lrow[LS_VALUE] = lv * vm; lrow[LS_ENT] = lent * vm; lrow[LS_KL] = kl * vm;
+      lrow[LS_CLIPFRAC] = cf * vm; lrow[LS_COUNT] = vm;
+      lrow[LS_COUNT + 1] = 0.f; lrow[LS_FIXED - 1] = 0.f;   // (the unused slots)
     }
   }
   __syncthreads();
@@ -517,15 +487,15 @@ __global__ __launch_bounds__(NW * 64, (TrainOcc<DT, NW>::V)) void mlp_train_kern
     // column q of [loss terms | dlog_std] summed over the tile's rows by a group of PG lanes
     // (fixed order: strided partials, then an xor tree) — deterministic
     constexpr int PG = 16;
-    for (int q0 = 0; q0 < NPART_FIXED + A; q0 += NT / PG) {
+    for (int q0 = 0; q0 < LS_FIXED + A; q0 += NT / PG) {
       const int q = q0 + tid / PG, g = tid % PG;
       float s = 0.f;
-      if (q < NPART_FIXED + A) {
-        if (q < NPART_FIXED) for (int r = g; r < ROWS; r += PG) s += LOSS[r * NPART_FIXED + q];
-        else for (int r = g; r < ROWS; r += PG) s += DLS[r * A + (q - NPART_FIXED)];
+      if (q < LS_FIXED + A) {
+        if (q < LS_FIXED) for (int r = g; r < ROWS; r += PG) s += LOSS[r * LS_FIXED + q];
+        else for (int r = g; r < ROWS; r += PG) s += DLS[r * A + (q - LS_FIXED)];
       }
       s = group_sum<PG>(s);
-      if (q < NPART_FIXED + A && g == 0) a.part[(size_t)blockIdx.x * a.npart + q] = s;
+      if (q < LS_FIXED + A && g == 0) a.part[(size_t)blockIdx.x * a.npart + q] = s;
     }
   }
   write_transposed<DT, ROWS, NT>(DMU, ldmu, A, a.g3pT, a.ldT, m0, tid);
@@ -562,7 +532,7 @@ size_t train_lds(const MlpArgs& a) {
   size_t b = train_region_bytes<DT, ROWS>(a);
   b += al(sizeof(T) * ROWS * ld(a.d_in[1]));
   b += al(sizeof(T) * ROWS * ld(a.d_in[4]));
-  b += al(sizeof(float) * ROWS * a.A) * 2 + al(sizeof(float) * ROWS) + al(sizeof(float) * ROWS * NPART_FIXED);
+  b += al(sizeof(float) * ROWS * a.A) * 2 + al(sizeof(float) * ROWS) + al(sizeof(float) * ROWS * LS_FIXED);
   return b;
 }
 

@@ -33,12 +33,11 @@
 #include <type_traits>
 
 #include "kernels.h"
+#include "loss_core.h"
 #include "mlp_core.h"
 
 namespace {
 
-constexpr float HD_LOG_2PI = 1.8378770664093453f;
-constexpr int NPF = 8;                      // fixed loss-term columns of a partial row
 constexpr int ROWS = 128;                   // rows per workgroup (both heads)
 constexpr int NSLOT = 16;                   // fragments per ring stage
 constexpr int SST = 36, TILE_F = 16 * SST;  // [16][SST] fp32 transpose tile (conflict-free)
@@ -189,8 +188,8 @@ template <int DT, bool F8 = false>
 constexpr bool head_lds_ok() {
   return head_lds_bytes<DT, 0>() <= 160 * 1024 && head_lds_bytes<DT, 1, F8>() <= 160 * 1024 &&
          // value: loss tile + partials + its 128 dW_v partials; policy: + the [64][20] h2^T image
-         wrows<1>() * SST + NPF + 32 + 128 <= xr_floats<DT, 1, F8>() &&
-         ((wrows<0>() * SST + NPF + 32 + 3) & ~3) + 64 * 20 <= xr_floats<DT, 0>() &&
+         wrows<1>() * SST + LS_FIXED + 32 + 128 <= xr_floats<DT, 1, F8>() &&
+         ((wrows<0>() * SST + LS_FIXED + 32 + 3) & ~3) + 64 * 20 <= xr_floats<DT, 0>() &&
          // the dW_mu tiles of 4 waves go through the policy ring
          4 * 32 * 128 * 4 <= head_stages<DT, 0>() * stage_bytes<DT>() &&
          // the observation DMAs lead the weight waits
@@ -1020,11 +1019,11 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
     return;
   } else {
   // (the transpose tiles hold mu / v from here: every wave's own)
-  float dls[JM], lt[6];
+  float dls[JM], lt[LS_COUNT + 1];
 #pragma unroll
   for (int q = 0; q < JM; ++q) dls[q] = 0.f;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) lt[k] = 0.f;
+  for (int k = 0; k <= LS_COUNT; ++k) lt[k] = 0.f;
   Frag ad[RB];   // the A operand of dgrad fc3: dL/dmu (policy) | dL/dv in column 0 (value)
   if constexpr (HEAD == 0) {
 #pragma unroll
@@ -1054,17 +1053,13 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
         if (j >= A) break;
         const float lsig = cvar * lsv[q];
         const float z = (actv[q] - mus[r * 32 + j]) * __expf(-lsig);
-        logp += -0.5f * z * z - 0.5f * HD_LOG_2PI - lsig;
+        logp += gauss_logp_dim(z, lsig);
       }
       logp = xsum<TPR - 1>(logp);
-      const float lrat = logp - l_lpo;
-      const float ratio = __expf(lrat);
-      const float s1 = ratio * l_adv;
-      const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * l_adv;
-      lclip = -fminf(s1, s2);
-      const float dlogp = (s1 <= s2) ? -l_adv * ratio : 0.f;
-      kl = (ratio - 1.f) - lrat;
-      cf = (fabsf(ratio - 1.f) > a.clip) ? 1.f : 0.f;
+      const Surrogate sg = ppo_surrogate(logp - l_lpo, l_adv, a.clip);
+      lclip = sg.loss;
+      kl = sg.kl;
+      cf = sg.clipped;
 #pragma unroll
       for (int q = 0; q < JM; ++q) {
         const int j = sub + TPR * q;
@@ -1072,9 +1067,10 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
         const float lsig = cvar * lsv[q];
         const float isig = __expf(-lsig);
         const float z = (actv[q] - mus[r * 32 + j]) * isig;
-        dml[r * SST + j] = valid ? dlogp * z * isig : 0.f;
-        dls[q] = valid ? (dlogp * (z * z - 1.f) - a.ent_coeff) * cvar : 0.f;
-        lent += -a.ent_coeff * (0.5f + 0.5f * HD_LOG_2PI + lsig);
+        const GaussGrad g = gauss_grad_dim(z, isig, sg.dlogp, a.ent_coeff, cvar);
+        dml[r * SST + j] = valid ? g.dmu : 0.f;
+        dls[q] = valid ? g.dls : 0.f;
+        lent += gauss_ent_dim(lsig, a.ent_coeff);
       }
       lent = xsum<TPR - 1>(lent);
     } else {
@@ -1090,20 +1086,13 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
         const float mu_o = first ? mu : mupv[q];
         const float var_o = first ? var : __expf(lsov[q]);
         const float x = actv[q];
-        const float pd = __expf(-(x - mu) * (x - mu) / (2.f * var)) * rsqrtf(2.f * var * 3.14159265358979f);
-        const float po = __expf(-(x - mu_o) * (x - mu_o) / (2.f * var_o)) * rsqrtf(2.f * var_o * 3.14159265358979f);
-        const float ratio = pd / (1e-10f + po);
-        const float s1 = ratio * l_adv;
-        const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * l_adv;
-        lclip += -fminf(s1, s2) * invA;
-        const float dratio = (s1 <= s2) ? -l_adv * invA : 0.f;
-        float dp = dratio / (1e-10f + po);
-        const float lgp = logf(pd + 1e-5f);
-        lent += -a.ent_coeff * pd * lgp * invA;
-        dp += -a.ent_coeff * invA * (lgp + pd / (pd + 1e-5f));
-        dml[r * SST + j] = valid ? dp * pd * (x - mu) / var : 0.f;
-        dls[q] = valid ? dp * pd * ((x - mu) * (x - mu) / (2.f * var) - 0.5f) : 0.f;
-        cf += (fabsf(ratio - 1.f) > a.clip) ? invA : 0.f;
+        const RefDim t = dppo_ref_dim(x, mu, var, mu_o, var_o, l_adv, a.clip, a.ent_coeff, invA, lclip, lent);
+        lclip = t.lclip;
+        lent = t.lent;
+        const float dp = dppo_ref_dp(t, l_adv, a.ent_coeff, invA);
+        dml[r * SST + j] = valid ? dppo_ref_dmu(dp, t.p, x, mu, var) : 0.f;
+        dls[q] = valid ? dppo_ref_dls(dp, t.p, x, mu, var) : 0.f;
+        cf += dppo_ref_cf(t, a.clip, invA);
         if (valid) a.mu_prev[(size_t)lsrc * A + j] = mu;   // train.py:164 model_old <- model
       }
       lclip = xsum<TPR - 1>(lclip);
@@ -1112,21 +1101,22 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
     }
     if (sub == 0) {
       const float vm = valid ? 1.f : 0.f;
-      lt[0] = lclip * vm; lt[2] = lent * vm; lt[3] = kl * vm; lt[4] = cf * vm; lt[5] = vm;
+      lt[LS_CLIP] = lclip * vm; lt[LS_ENT] = lent * vm; lt[LS_KL] = kl * vm; lt[LS_CLIPFRAC] = cf * vm;
+      lt[LS_COUNT] = vm;
     }
     // the wave's partial sums over its 32 rows (lanes of one sub-lane: xor over lane bits 1-5)
 #pragma unroll
     for (int q = 0; q < JM; ++q) dls[q] = xsum<63 & ~(TPR - 1)>(dls[q]);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) lt[k] = xsum<63 & ~(TPR - 1)>(lt[k]);
+    for (int k = 0; k <= LS_COUNT; ++k) lt[k] = xsum<63 & ~(TPR - 1)>(lt[k]);
     if (lane < TPR) {
 #pragma unroll
       for (int q = 0; q < JM; ++q)
-        if (lane + TPR * q < A) wpart[NPF + lane + TPR * q] = dls[q];
+        if (lane + TPR * q < A) wpart[LS_FIXED + lane + TPR * q] = dls[q];
       if (lane == 0) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) wpart[k] = lt[k];
-        wpart[6] = wpart[7] = 0.f;
+        for (int k = 0; k <= LS_COUNT; ++k) wpart[k] = lt[k];
+        wpart[LS_COUNT + 1] = wpart[LS_FIXED - 1] = 0.f;   // (the unused slots)
       }
     }
 #pragma unroll
@@ -1144,35 +1134,21 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
       const bool first = a.first_step != 0;
       const float vold = ref_loss ? (first ? v : l_vprev) : l_vold;
       float lv;
-      if (a.value_loss == 0) {
-        const float d = v - l_ret;
-        lv = d * d;
-        dv = 2.f * d;
-      } else {
-        const float d1 = v - l_ret;
-        const float dd = v - vold;
-        const float vc = vold + fminf(fmaxf(dd, -a.clip), a.clip);
-        const float d2 = vc - l_ret;
-        const float f1 = d1 * d1, f2 = d2 * d2;
-        const float inr = (dd >= -a.clip && dd <= a.clip) ? 1.f : 0.f;
-        lv = 0.5f * fmaxf(f1, f2);
-        if (f1 > f2) dv = d1;
-        else if (f2 > f1) dv = d2 * inr;
-        else dv = 0.5f * d1 + 0.5f * d2 * inr;
-      }
+      if (a.value_loss == 0) value_mse(v - l_ret, lv, dv);
+      else value_clipped_half(v - l_ret, v, l_ret, vold, a.clip, lv, dv);
       if (ref_loss && valid) a.v_prev[lsrc] = v;
       dv = valid ? dv : 0.f;
       const float vm = valid ? 1.f : 0.f;
-      lt[1] = lv * vm;
-      lt[5] = vm;
+      lt[LS_VALUE] = lv * vm;
+      lt[LS_COUNT] = vm;
       dml[lrow] = dv;   // dL/dv of the wave's 32 rows
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) lt[k] = xsum<WROWS - 1>(lt[k]);
+    for (int k = 0; k <= LS_COUNT; ++k) lt[k] = xsum<WROWS - 1>(lt[k]);
     if (lane == 0) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) wpart[k] = lt[k];
-      wpart[6] = wpart[7] = 0.f;
+      for (int k = 0; k <= LS_COUNT; ++k) wpart[k] = lt[k];
+      wpart[LS_COUNT + 1] = wpart[LS_FIXED - 1] = 0.f;   // (the unused slots)
     }
     // the A operand of dgrad fc3 (K = 32, only k = 0 nonzero)
     float dvr[RB];
@@ -1198,7 +1174,7 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(q0) : "v"(base + 16u * (4 * rb + lg)) : "memory");
         dq[rb] = f32x4{q0.x, q0.y, q0.z, q0.w};
       }
-      float* wdw = wpart + NPF + 32;
+      float* wdw = wpart + LS_FIXED + 32;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         float sacc = 0.f;
@@ -1324,7 +1300,7 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
       am2[m] = H::from8(x);
     }
     constexpr int HLD = 20;                                    // [64 features][HLD] (16 rows + pad)
-    float* h2t = dml + ((WROWS * SST + NPF + 32 + 3) & ~3);    // after the loss tile + partials
+    float* h2t = dml + ((WROWS * SST + LS_FIXED + 32 + 3) & ~3);    // after the loss tile + partials
     static_for<0, 2>([&](auto hc) __attribute__((always_inline)) {
       constexpr int hh = decltype(hc)::value;
 #pragma unroll
@@ -1399,17 +1375,17 @@ __global__ __launch_bounds__(HeadCfg<HEAD>::NW * 64, 1) void mlp_head_kernel(Mlp
     float* dst = a.part + (size_t)blockIdx.x * a.npart + a.part_dw;
     if (tid < 128) {
       float sv = 0.f;
-      for (int w = 0; w < NW; ++w) sv += sc1[w * WS_F + WROWS * SST + NPF + 32 + tid];
+      for (int w = 0; w < NW; ++w) sv += sc1[w * WS_F + WROWS * SST + LS_FIXED + 32 + tid];
       dst[tid] = sv;
     }
   }
-  // (each head writes only its own columns — policy: loss terms 0, 2-7 and the A dlog_std;
-  // value: the value-loss column 1 — so both kernels can share one partial buffer)
+  // (each head writes only its own columns — policy: every loss term but LS_VALUE and the A dlog_std;
+  // value: LS_VALUE alone — so both kernels can share one partial buffer)
   const float* sc0 = reinterpret_cast<const float*>(smem + (size_t)S * SB);
-  const int np = HEAD == 0 ? NPF + A : 1;
+  const int np = HEAD == 0 ? LS_FIXED + A : 1;
   for (int i = tid; i < np; i += NW * 64) {
-    const int q = HEAD == 0 ? (i == 1 ? NPF + A : i) : 1;   // (policy: column 1 is the value's)
-    if (q >= NPF + A) continue;
+    const int q = HEAD == 0 ? (i == LS_VALUE ? LS_FIXED + A : i) : LS_VALUE;   // (policy: LS_VALUE is the value's)
+    if (q >= LS_FIXED + A) continue;
     float s = 0.f;
     for (int w = 0; w < NW; ++w) s += sc0[w * WS_F + WROWS * SST + q];
     a.part[(size_t)blockIdx.x * a.npart + q] = s;

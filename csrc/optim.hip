@@ -471,7 +471,7 @@ __global__ __launch_bounds__(256) void gather_adam_kernel(
 
 // target_kl: the gate, one launch after every step (ops/oracle.py kl_gate).  It is the only writer
 // of gate and, in gated mode, of the step counter: if the step just enqueued was applied (stop was
-// 0) the counter advances; then kl = fl32(sums[3] / max(sums[5], 1)) of that step's loss sums is
+// 0) the counter advances; then kl = fl32(sums[LS_KL] / max(sums[LS_COUNT], 1)) of that step's loss sums is
 // held against the target.  !(kl <= target), so a NaN trips too; a set stop stays set.
 // lr_schedule adaptive (ops/oracle.py lr_adapt): with a rate block, the same thread is the only writer
 // of lr_state = [lr, downs, ups, reserved] — after an APPLIED step its kl moves the rate the next
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(64) void kl_gate_kernel(const float* __restrict__ s
     state[1] = step;
     gate[1] += 1.f;
   }
-  const float kl = __fdiv_rn(sums[3], fmaxf(sums[5], 1.f));
+  const float kl = __fdiv_rn(sums[LS_KL], fmaxf(sums[LS_COUNT], 1.f));
   gate[3] = kl;
   if (open && !(kl <= target)) {
     gate[0] = 1.f;

@@ -18,12 +18,13 @@
 //   * the row-major wgrad operand g1 [ldT][128] (csrc/wgrad.hip RM reads) and, for a minibatch
 //     (idx != null, !xT_ready), the observation rows [ldT][d0]
 //     (full-batch calls: the wgrad reads x_buf itself — no x^T copy anywhere);
-//   * per-workgroup partials: loss terms (columns 0, 2-7), dlog_std (8 + j), the mu layer's weight
+//   * per-workgroup partials: loss terms (the LossSlot columns but LS_VALUE), dlog_std (LS_FIXED + j), the mu layer's weight
 //     gradient dW_mu [32][128] at part_dw (bias = column 100) and p_fc2's dW_p2 [128][128] right
 //     after it (bias = column 100), each summed over the workgroup's 128 rows by MFMA with the
 //     batch as K: the operands are staged row-major in LDS and read back transposed
 //     (ds_read_b64_tr_b16).  So only p_fc1's operands (g1 and the observation rows) go through
 //     HBM to the wgrad.
+#include "loss_core.h"
 #include "t32.h"
 
 namespace {
@@ -37,7 +38,7 @@ constexpr int PH_S = 3;                 // ring stages
 constexpr int PH_GL = 2;                // ring DMA instructions per wave and stage
 constexpr int PH_XS = 3, PH_XB = 2048;  // X ring slots per wave / bytes per slot
 constexpr int PH_SCR = 48 * 1024;       // X rings (fc1) | dW_mu staging: h2 half [128][64] + dL/dmu [128][32], hi | lo
-constexpr int PH_RED = 64;              // per wave: 8 loss terms | 32 dlog_std (floats)
+constexpr int PH_RED = 64;              // per wave: LS_FIXED loss terms | 32 dlog_std (floats)
 constexpr int PH_HP = 128 * 64 * 2;     // one precision plane of the staged h2 half (bytes)
 constexpr int PH_DP = 128 * 32 * 2;     // one precision plane of the staged dL/dmu
 
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
   // ---- the policy loss of this lane's row (dims ph_dim(i, h)) -> dL/dmu, dlog_std, loss terms ----
   f32x16 dmu;
   float dls[16];
-  float lt[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float lt[LS_COUNT + 1] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   {
     const float cvar = a.std_var ? 0.5f : 1.f;
     const float vm = valid ? 1.f : 0.f;
@@ -373,33 +374,30 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
         if (d < A) {
           const float lsig = cvar * lsd[d];
           const float z = (acts[d * 32 + r] - mu[i]) * __expf(-lsig);
-          lp += -0.5f * z * z - 0.5f * T32_LOG_2PI - lsig;
-          lent += -a.ent_coeff * (0.5f + 0.5f * T32_LOG_2PI + lsig);
+          lp += gauss_logp_dim(z, lsig);
+          lent += gauss_ent_dim(lsig, a.ent_coeff);
         }
       }
       const float logp = lp + __shfl_xor(lp, 32, 64);
-      const float lrat = logp - l_lpo;
-      const float ratio = __expf(lrat);
-      const float s1 = ratio * l_adv;
-      const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * l_adv;
-      const float dlogp = (s1 <= s2) ? -l_adv * ratio : 0.f;
+      const Surrogate sg = ppo_surrogate(logp - l_lpo, l_adv, a.clip);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int d = ph_dim(i, h);
         const float lsig = cvar * lsd[d & 31];
         const float isig = __expf(-lsig);
         const float z = (acts[(d < A ? d : 0) * 32 + r] - mu[i]) * isig;
+        const GaussGrad g = gauss_grad_dim(z, isig, sg.dlogp, a.ent_coeff, cvar);
         const bool on = valid && d < A;
-        dmu[i] = on ? dlogp * z * isig : 0.f;
-        dls[i] = on ? (dlogp * (z * z - 1.f) - a.ent_coeff) * cvar : 0.f;
+        dmu[i] = on ? g.dmu : 0.f;
+        dls[i] = on ? g.dls : 0.f;
       }
       if (h == 0) {
-        lt[0] = -fminf(s1, s2) * vm;
-        lt[3] = ((ratio - 1.f) - lrat) * vm;
-        lt[4] = (fabsf(ratio - 1.f) > a.clip ? 1.f : 0.f) * vm;
-        lt[5] = vm;
+        lt[LS_CLIP] = sg.loss * vm;
+        lt[LS_KL] = sg.kl * vm;
+        lt[LS_CLIPFRAC] = sg.clipped * vm;
+        lt[LS_COUNT] = vm;
       }
-      lt[2] = lent * vm;
+      lt[LS_ENT] = lent * vm;
     } else {
       // reference DPPO loss (train.py:142-161): per-dim pdf ratio, variance convention
       const float invA = 1.f / (float)A;
@@ -416,42 +414,35 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
           const float mu_o = first ? m : a.mu_prev[(size_t)srow * A + d];
           const float var_o = first ? var : __expf(lsd[32 + d]);
           const float x = acts[d * 32 + r];
-          const float pd = __expf(-(x - m) * (x - m) / (2.f * var)) * rsqrtf(2.f * var * 3.14159265358979f);
-          const float po = __expf(-(x - mu_o) * (x - mu_o) / (2.f * var_o)) * rsqrtf(2.f * var_o * 3.14159265358979f);
-          const float ratio = pd / (1e-10f + po);
-          const float s1 = ratio * l_adv;
-          const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * l_adv;
-          lclip += -fminf(s1, s2) * invA;
-          const float dratio = (s1 <= s2) ? -l_adv * invA : 0.f;
-          float dp = dratio / (1e-10f + po);
-          const float lgp = logf(pd + 1e-5f);
-          lent += -a.ent_coeff * pd * lgp * invA;
-          dp += -a.ent_coeff * invA * (lgp + pd / (pd + 1e-5f));
-          dmu[i] = valid ? dp * pd * (x - m) / var : 0.f;
-          dls[i] = valid ? dp * pd * ((x - m) * (x - m) / (2.f * var) - 0.5f) : 0.f;
-          cf += (fabsf(ratio - 1.f) > a.clip) ? invA : 0.f;
+          const RefDim t = dppo_ref_dim(x, m, var, mu_o, var_o, l_adv, a.clip, a.ent_coeff, invA, lclip, lent);
+          lclip = t.lclip;
+          lent = t.lent;
+          const float dp = dppo_ref_dp(t, l_adv, a.ent_coeff, invA);
+          dmu[i] = valid ? dppo_ref_dmu(dp, t.p, x, m, var) : 0.f;
+          dls[i] = valid ? dppo_ref_dls(dp, t.p, x, m, var) : 0.f;
+          cf += dppo_ref_cf(t, a.clip, invA);
           if (valid) a.mu_prev[(size_t)srow * A + d] = m;   // train.py:164 model_old <- model
         }
       }
-      lt[0] = lclip * vm;
-      lt[2] = lent * vm;
-      lt[4] = cf * vm;
-      if (h == 0) lt[5] = vm;
+      lt[LS_CLIP] = lclip * vm;
+      lt[LS_ENT] = lent * vm;
+      lt[LS_CLIPFRAC] = cf * vm;
+      if (h == 0) lt[LS_COUNT] = vm;
     }
   }
   // the wave's sums over its 32 rows (fixed order): loss terms over all 64 lanes, dlog_std per dim
 #pragma unroll
-  for (int k = 0; k < 6; ++k)
+  for (int k = 0; k <= LS_COUNT; ++k)
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) lt[k] += __shfl_xor(lt[k], m, 64);
   {
     const float s = half_sum16(dls, lane);
     float* wr = red + wave * PH_RED;
-    if (r < 16) wr[8 + ph_dim(r, h)] = s;
+    if (r < 16) wr[LS_FIXED + ph_dim(r, h)] = s;
     if (lane == 0) {
 #pragma unroll
-      for (int k = 0; k < 6; ++k) wr[k] = lt[k];
-      wr[6] = wr[7] = 0.f;
+      for (int k = 0; k <= LS_COUNT; ++k) wr[k] = lt[k];
+      wr[LS_COUNT + 1] = wr[LS_FIXED - 1] = 0.f;   // (the unused slots)
     }
   }
   // dL/dmu as B operands (dims 0-15, 16-31) of the mu dgrad
@@ -695,7 +686,7 @@ __global__ __launch_bounds__(PH_WAVES * 64, 2) void phead_kernel(MlpArgs a) {
   // (no DMA is in flight: the last stage's sync waited for all of them; the operand stores may
   // drain after the waves end)
   float* dst = a.part + (size_t)blockIdx.x * a.npart;
-  if (tid < 8 + A && tid != 1) {
+  if (tid < LS_FIXED + A && tid != LS_VALUE) {
     dst[tid] = ((red[tid] + red[PH_RED + tid]) + red[2 * PH_RED + tid]) + red[3 * PH_RED + tid];
   }
 }

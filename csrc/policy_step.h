@@ -12,8 +12,6 @@
 #include "kernels.h"
 #include "mlp_core.h"
 
-constexpr float LOG_2PI_F = 1.8378770664093453f;
-
 DEV float norm_clamp(float o, float mean, float inv_std) { return fminf(fmaxf((o - mean) * inv_std, -5.f), 5.f); }
 // columns [O, d1) of the input tile: the constant 1 (fc1's bias input), then zeros
 DEV float pad_col(int d, int O) { return (d == O) ? 1.f : 0.f; }

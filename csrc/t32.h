@@ -13,8 +13,6 @@
 
 namespace t32 {
 
-constexpr float T32_LOG_2PI = 1.8378770664093453f;
-
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2v;

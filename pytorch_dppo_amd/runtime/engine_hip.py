@@ -35,7 +35,11 @@ from ..utils.obs_stats import RunningObsStats
 from ..utils.ret_stats import VAR_FLOOR as RET_VAR_FLOOR, RunningReturnStats
 from .engine import Engine, check_discrete
 from .engine_torch import load_ret_acc
-from .metrics_layout import NPART_FIXED, MetricsLayout
+from .metrics_layout import LOSS_SLOTS, NPART_FIXED, MetricsLayout
+
+# the loss row's slots (csrc/kernels.h LossSlot) as indices, for losses_from_vector
+_LS_CLIP, _LS_VALUE, _LS_ENT, _LS_KL, _LS_CLIPFRAC, _LS_COUNT = (
+    LOSS_SLOTS.index(k) for k in ("clip", "value", "ent", "kl", "clipfrac", "count"))
 
 STORAGE = storage.STORAGE
 Q8_SX, Q8_SH = 64.0, 256.0   # fixed e4m3 operand scales of the observations / tanh activations (csrc/common.h)
@@ -1834,9 +1838,9 @@ class HipEngine(Engine):
 
     @staticmethod
     def losses_from_vector(v) -> Dict[str, float]:
-        n = max(v[5], 1.0)
-        out = {"loss_clip": v[0] / n, "loss_value": v[1] / n, "loss_ent": v[2] / n,
-               "approx_kl": v[3] / n, "clipfrac": v[4] / n}
+        n = max(v[_LS_COUNT], 1.0)
+        out = {"loss_clip": v[_LS_CLIP] / n, "loss_value": v[_LS_VALUE] / n, "loss_ent": v[_LS_ENT] / n,
+               "approx_kl": v[_LS_KL] / n, "clipfrac": v[_LS_CLIPFRAC] / n}
         out["loss"] = out["loss_clip"] + out["loss_value"] + out["loss_ent"]
         out["grad_norm"] = float(v[NPART_FIXED])
         return out

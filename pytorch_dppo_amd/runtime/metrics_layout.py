@@ -16,7 +16,9 @@ of the same layout from ``engine.metrics_tails()``, and ``decode`` names the fie
 """
 from __future__ import annotations
 
-NPART_FIXED = 8      # the loss sums of one update step (csrc: the fixed slots of a loss partial)
+NPART_FIXED = 8      # the loss sums of one update step (csrc/kernels.h LS_FIXED: the fixed slots of a loss partial)
+# the used slots by name, in the order of csrc/kernels.h LossSlot (LS_CLIP .. LS_COUNT); the rest stay 0
+LOSS_SLOTS = ("clip", "value", "ent", "kl", "clipfrac", "count")
 
 
 class MetricsLayout:

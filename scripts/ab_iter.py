@@ -3,7 +3,9 @@
 Arms run interleaved in ONE process on ONE worker (same box, same clocks): each round runs K
 deferred iterations per arm (the bench's production loop) and reports ms per iteration.
 
-    python scripts/ab_iter.py bf16x3 A,b,c [rounds] [iters] [untimed rounds]
+    python scripts/ab_iter.py bf16x3 A,b,c [rounds] [iters] [untimed rounds] [update kernels]
+
+(`update kernels`: auto | heads | tile, Params.update_kernels; "tile" puts `mlp_train` on the bench geometry's path.)
 
 (The first round of a process runs 0.1-0.15 ms per iteration above the later ones on every arm —
 clocks and caches still settling after the two warm-up iterations — so a max - min spread over
@@ -36,11 +38,12 @@ def main():
     rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 4
     iters = int(sys.argv[4]) if len(sys.argv) > 4 else 10
     untimed = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+    kernels = sys.argv[6] if len(sys.argv) > 6 else "auto"
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ctx = init_single_rank_collective(dev, port=free_port())
     p = dppo_preset(device="gpu", env_name="Humanoid-v2", num_envs=4096, exploration_size=65536, batch_size=65536,
-                    dtype=dtype, seed=1, phase_timing=0)
+                    dtype=dtype, seed=1, phase_timing=0, update_kernels=kernels)
     w = DPPOWorker(p, ctx)
     ext = w.engine.ext
     from pytorch_dppo_amd.ops import native
@@ -102,7 +105,8 @@ def main():
                 res[k].append((time.perf_counter() - t0) / iters * 1e3)
     out = {k: {"median_ms": sorted(v)[len(v) // 2], "spread_ms": round(max(v) - min(v), 3), "all_ms": [round(x, 3) for x in v]}
            for k, v in res.items()}
-    print(json.dumps({"dtype": dtype, "untimed_rounds": untimed, "arms": out}))
+    print(json.dumps({"dtype": dtype, "update_kernels": kernels, "heads": bool(w.engine.heads), "untimed_rounds": untimed,
+                      "arms": out}))
     ctx.destroy()
 
 

@@ -9,7 +9,8 @@ runs two iterations of two epochs; after each it writes, as ``DIR/<config>/it<k>
 ``adam_m``, ``adam_v``, ``adam_state``, ``grad_flat``, ``loss_sums``, ``norm_part[:_norm_n]``, ``wimg`` (raw storage
 bytes), ``wimg_fwd`` and ``q8_amax`` in fp8 mode, and ``mu_prev`` / ``v_prev`` under the reference loss.
 
-Sizes: Humanoid-v2 dims (the per-head kernels need the reference network), 64 envs x 8 steps = 512 rows.
+Sizes: Humanoid-v2 dims (the per-head kernels need the reference network; CartPole-v1 its own), 64 envs x 8 steps
+= 512 rows.
 Minibatch 512: the full batch, whole 128-row workgroups, the x^T-ready path; 200: gathered rows, masked rows in the
 last workgroup.  Two epochs: ``first_step`` on and off, and all three slots of the fp8 amax ring.  Configurations:
 
@@ -17,7 +18,8 @@ last workgroup.  Two epochs: ``first_step`` on and off, and all three slots of t
   heads: also phead_kernel on | off  x  phead_fused_dw2 on | off
   heads at fp8: also fp8_wgrad_operands on | off  x  fp8_policy_gemms on | off
   extras, on both kernel families at bf16x3 and bf16: loss dppo_ref, value_loss clipped_half, max_grad_norm 0.5,
-      compat (the extra gradient), fused_apply off, target_kl
+      compat (the extra gradient), fused_apply off, target_kl, adv_norm_scope minibatch (advnorm)
+  CartPole-v1 (a discrete env: the categorical head, the tile kernel alone) at fp32 | bf16x3 | bf16, minibatch 200
 
 A combination the configuration or the engine refuses is skipped; ``DIR/skips.json`` lists each with the refusal's
 text and ``DIR/configs.json`` the ones that ran.  The multi-rank branches of ``step()`` (in-stream, side-stream
@@ -42,7 +44,7 @@ E, T, ITERS, EPOCHS = 64, 8, 2, 2
 TARGET_KL = 2.43e-3
 EXTRAS = (("dpporef", dict(loss="dppo_ref", std_convention="var")), ("vclip", dict(value_loss="clipped_half")),
           ("clip", dict(max_grad_norm=0.5)), ("compat", dict(compat=True)), ("unfused", dict(fused_apply=False)),
-          ("kl", dict(target_kl=TARGET_KL)))
+          ("kl", dict(target_kl=TARGET_KL)), ("advnorm", dict(normalize_adv=True, adv_norm_scope="minibatch")))
 
 
 def configs():
@@ -60,6 +62,9 @@ def configs():
                                  fp8_policy_gemms=pg)))
     for (tag, kw), fam, dtype in itertools.product(EXTRAS, ("tile", "heads"), ("bf16x3", "bf16")):
         out.append((f"extra-{tag}-{fam}-{dtype}", dict(dtype=dtype, update_kernels=fam, batch_size=200, **kw)))
+    for dtype in ("fp32", "bf16x3", "bf16"):
+        out.append((f"cartpole-tile-{dtype}-mb200",
+                    dict(env_name="CartPole-v1", dtype=dtype, update_kernels="tile", batch_size=200)))
     return out
 
 

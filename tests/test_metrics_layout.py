@@ -1,11 +1,14 @@
 """The metrics vector's layout (runtime/metrics_layout.py): sizes, slices and decode over every feature combination."""
 import itertools
+import os
+import re
 
 import pytest
 
 from pytorch_dppo_amd.config import dppo_preset
-from pytorch_dppo_amd.runtime.metrics_layout import MetricsLayout
+from pytorch_dppo_amd.runtime.metrics_layout import LOSS_SLOTS, NPART_FIXED, MetricsLayout
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORDER = ("ep", "loss", "return_std", "gate", "lr", "adv")
 LR_WIDTH = {"constant": 0, "linear": 1, "adaptive": 3}
 
@@ -41,6 +44,25 @@ def test_layout_size_slices_and_decode(reward_norm, target_kl, lr_schedule, adv_
         assert f[name] == (v[lay[name]] if want[name] else None), name
     with pytest.raises(ValueError):
         lay.decode(v + [0.0])
+
+
+def test_loss_slots_match_the_kernels_enum():
+    """LOSS_SLOTS names the slots of the loss row in the order of csrc/kernels.h's LossSlot, and NPART_FIXED is its
+    LS_FIXED: the enum is read from the header's text (C rule: an enumerator without a value is its predecessor + 1)."""
+    with open(os.path.join(ROOT, "csrc", "kernels.h")) as f:
+        m = re.search(r"enum\s+LossSlot\s*\{([^}]*)\}", f.read())
+    assert m is not None
+    slots, nxt = {}, 0
+    for item in m.group(1).split(","):
+        e = re.fullmatch(r"\s*(LS_[A-Z]+)\s*(?:=\s*(\d+))?\s*", item)
+        assert e is not None, item
+        nxt = int(e.group(2)) if e.group(2) is not None else nxt
+        slots[e.group(1)] = nxt
+        nxt += 1
+    assert slots.pop("LS_FIXED") == NPART_FIXED
+    assert slots == {"LS_" + name.upper(): i for i, name in enumerate(LOSS_SLOTS)}
+    assert list(slots) == ["LS_" + name.upper() for name in LOSS_SLOTS]      # written in that order, too
+    assert len(LOSS_SLOTS) <= NPART_FIXED
 
 
 def test_sizes_the_gpu_tests_pin():
