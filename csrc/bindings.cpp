@@ -127,12 +127,22 @@ PolicyNet policy_net(int64_t dt, const Layout& L, const torch::Tensor& wimg, con
 }
 
 // The env fields RolloutArgs and EvalArgs share (ints kind,E,O,A,S lead both bindings' lists): the env kind
-// against its state / observation / action dims (O, A >= 1) and the layout, and the four stream keys
-template <class Args> void check_env(const Args& a, const Layout& L) {
+// against its state / observation / action dims (O, A >= 1) and the layout, and the four stream keys.
+// dist (the optional last int of both lists, default 0): the policy head.  1, the categorical head, exists on
+// the cart-pole's physics alone (two pushes: A == 2), for 16-row tiles (rows: the rollout's tile; the
+// evaluation's is 16) and not in fp8; the rollout's per-step filter refuses it too (rollout_stepnorm).
+template <class Args> void check_env(const Args& a, const Layout& L, int64_t dt, int64_t rows) {
   TORCH_CHECK(a.kind >= 0 && a.kind <= 2, "kind must be 0 (synthetic), 1 (pendulum) or 2 (cart-pole), got ", a.kind);
+  TORCH_CHECK(a.dist == 0 || a.dist == 1, "dist: 0 Gaussian, 1 categorical, got ", a.dist);
+  TORCH_CHECK(a.dist == 0 || a.kind == 2, "dist 1 (the categorical head) runs on the cart-pole's physics (kind 2) only: "
+              "the other in-kernel envs take continuous actions, got kind ", a.kind);
   TORCH_CHECK(a.O >= 1 && a.A >= 1, "O / A");
-  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3) : (a.S == 4 && a.O == 4 && a.A == 1),
+  TORCH_CHECK(a.kind == 0 ? a.S == a.O : a.kind == 1 ? (a.S == 2 && a.O == 3)
+                                                      : (a.S == 4 && a.O == 4 && a.A == (a.dist == 1 ? 2 : 1)),
               "state dims");
+  TORCH_CHECK(a.dist == 0 || dt != 2, "dist 1 (the categorical head) has no fp8 form: a categorical update runs on the "
+              "tile kernel, which fp8 does not take");
+  TORCH_CHECK(a.dist == 0 || rows == 16, "dist 1 (the categorical head) is built for 16-row tiles, got rows = ", rows);
   TORCH_CHECK(L.n_out[2] == a.A && L.d_in[0] == ((a.O + 1 + 31) / 32) * 32, "layout/env mismatch");
 }
 template <class Args> void env_keys(Args& a, Ints keys) {
@@ -147,7 +157,7 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_re
                          const std::vector<double>& scales, CT flat, CT mean, CT inv_std, CT shift, CT x_out, CT actions,
                          CT logp, CT rewards, CT dones, CT mom, CT epstat, Ints ints, Ints keys, double reward_clip,
                          CT qscale, CT xT_out, int64_t xT_rows) {
-  TORCH_CHECK(ints.size() == 11, "ints: kind,E,O,A,S,T,t_base,buf_E,t0,limit,std_var");
+  TORCH_CHECK(ints.size() == 11 || ints.size() == 12, "ints: kind,E,O,A,S,T,t_base,buf_E,t0,limit,std_var[,dist]");
   RolloutArgs a{};
   env_keys(a, keys);
   TORCH_CHECK(rows == 16 || rows == 32, "rows must be 16 or 32");
@@ -155,8 +165,9 @@ RolloutArgs rollout_args(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_re
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.T = (int)ints[5]; a.t_base = (int)ints[6]; a.buf_E = (int)ints[7]; a.t0 = (uint32_t)ints[8];
   a.limit = (int)ints[9];
+  a.dist = ints.size() == 12 ? (int)ints[11] : 0;
   TORCH_CHECK(a.E > 0 && a.T >= 1 && a.buf_E == a.E, "bad E/T");
-  check_env(a, L);
+  check_env(a, L, dt, rows);
   const int nblk = (a.E + (int)rows - 1) / (int)rows;
   check(state, "state", at::kFloat, (int64_t)a.E * a.S);
   check(ep_len, "ep_len", at::kInt, a.E);
@@ -250,6 +261,8 @@ void rollout_stepnorm(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_ret, 
   RolloutArgs a = rollout_args(dt, rows, state, ep_len, ep_ret, wimg, layout, scales, flat, sn[2], sn[3], shift,
                                x_out, actions, logp, rewards, dones, mom, epstat, ints, keys, reward_clip, qscale,
                                torch::Tensor(), 0);
+  TORCH_CHECK(a.dist == 0, "dist 1 (the categorical head) is not built into the per-step observation filter's launch "
+              "forms (obs_norm_update = step): they are the register-tight 4-wave forms");
   TORCH_CHECK(a.t_base == 0, "the per-step normalisation launch covers the whole rollout");
   const int nblk = (a.E + (int)rows - 1) / (int)rows;
   check(sn[0], "sn mean", at::kDouble, a.O);
@@ -275,12 +288,12 @@ void rollout_stepnorm(int64_t dt, int64_t rows, CT state, CT ep_len, CT ep_ret, 
 
 // Batched policy evaluation (csrc/eval.hip): E fresh envs run to the end of their first episode;
 // writes ret [E] fp32 / len [E] int32 and nothing else.  ints: kind,E,O,A,S,limit,std_var,
-// deterministic; keys: env,term,reset,action.
+// deterministic and optionally dist (check_env); keys: env,term,reset,action.
 void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, std::vector<double> scales,
                   torch::Tensor flat, torch::Tensor mean, torch::Tensor inv_std, torch::Tensor ret, torch::Tensor len,
                   std::vector<int64_t> ints, std::vector<int64_t> keys, torch::Tensor qscale) {
   TORCH_CHECK(dt >= 0 && dt <= 3, "dt");
-  TORCH_CHECK(ints.size() == 8, "ints: kind,E,O,A,S,limit,std_var,deterministic");
+  TORCH_CHECK(ints.size() == 8 || ints.size() == 9, "ints: kind,E,O,A,S,limit,std_var,deterministic[,dist]");
   EvalArgs a{};
   env_keys(a, keys);
   TORCH_CHECK(scales.size() >= 3, "scales");
@@ -289,7 +302,8 @@ void eval_rollout(int64_t dt, torch::Tensor wimg, std::vector<int64_t> layout, s
   TORCH_CHECK(ints[5] >= 1 && ints[5] <= (int64_t)1 << 20, "limit must be in [1, 2^20], got ", ints[5]);
   a.kind = (int)ints[0]; a.E = (int)ints[1]; a.O = (int)ints[2]; a.A = (int)ints[3]; a.S = (int)ints[4];
   a.limit = (int)ints[5]; a.deterministic = ints[7] ? 1 : 0;
-  check_env(a, L);
+  a.dist = ints.size() == 9 ? (int)ints[8] : 0;
+  check_env(a, L, dt, 16);
   a.net = policy_net(dt, L, wimg, scales, flat, a.A, ints[6] ? 1 : 0, qscale);
   check(mean, "mean", at::kFloat, a.O);
   check(inv_std, "inv_std", at::kFloat, a.O);

@@ -46,7 +46,10 @@ struct EvalLds {
       : cv(smem), O(a.O), A(a.A), S(a.S), t(cv, a.net, ROWS, a.A) {}
 };
 
-template <int DT, int ROWS, int NW>
+// CAT: the categorical head (EvalArgs::dist 1) on the cart-pole's physics, as the rollout kernel's: phases (c)
+// and (d) are one per-env phase and the env kind a constant.  A template parameter so that the Gaussian forms
+// keep their instructions.
+template <int DT, int ROWS, int NW, bool CAT = false>
 __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
   using P = Prec<DT>;
   constexpr int NTHR = 64 * NW;
@@ -56,16 +59,18 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
   const int nvalid = min(ROWS, a.E - e0);
   const int O = a.O, A = a.A, S = a.S;
   const bool det = a.deterministic != 0;
+  const int kind = CAT ? KIND_CARTPOLE : a.kind;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const EvalLds<DT, ROWS> L(smem, a);
   PolicyStep<DT, ROWS, NW> ps(a.net, L.t);
-  // deterministic: the action IS mu (no sample phase, no copy)
-  const float* act = det ? L.t.mu : L.actb;
+  // deterministic: the action IS mu (no sample phase, no copy).  CAT: actb is the push row [ROWS][1]
+  const float* act = (det && !CAT) ? L.t.mu : L.actb;
+  const int actA = CAT ? 1 : A;
 
   // ---- reset the envs in LDS (every row of the tile: rows past E are stepped but never read
   // out), zero the padded activation tiles ----
-  env_reset_fresh<ROWS, NTHR>(a.kind, L.st, S, a.key_reset, e0, tid);
+  env_reset_fresh<ROWS, NTHR>(kind, L.st, S, a.key_reset, e0, tid);
   for (int d = tid; d < O; d += NTHR) { L.nm[d] = a.mean[d]; L.ninv[d] = a.inv_std[d]; }
   syn_tables(L.wdrv, L.jdx, S, A, tid, NTHR);
   ps.setup(L.lsg, tid);
@@ -82,7 +87,7 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
   // loop bound alone ends the launch
   for (int step = 0; step < a.limit; ++step) {
     // ---- (a) observe, normalise -> LDS tile ----
-    env_kind_switch(a.kind, [&](auto kind_tag) {
+    env_kind_switch(kind, [&](auto kind_tag) {
       constexpr int KIND = decltype(kind_tag)::value;
       for (int d = tid; d < a.net.d1; d += NTHR) {
         float m = 0.f, is = 1.f;
@@ -105,7 +110,7 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
     // ---- (b) policy MLP ----
     ps.layers(wave, lane);
     // ---- (c) stochastic: a = mu + sigma * eps ----
-    if (!det) {   // (a kernel argument: the barrier below is workgroup-uniform)
+    if (!CAT && !det) {   // (a kernel argument: the barrier below is workgroup-uniform)
       sample_loop<ROWS, NTHR>(L.kes, A, tid, true, [&](int r, int j, float eps) {
         L.actb[r * A + j] = L.t.mu[r * A + j] + L.lsg[A + j] * eps;
       });
@@ -117,14 +122,22 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
       const int r = tid / LPE, l = tid - r * LPE;
       float err = 0.f;
       const int na = min(A, O);
-      if (a.kind == 0) {
-        for (int j = l; j < na; j += LPE) err += syn_err_term(act[r * A + j], L.st[r * S + j]);
-      }
+      if constexpr (CAT) {
+        // mu holds the row's A logits (fc3's barrier published them and the key prefixes): the Gumbel-max sample,
+        // or the arg-max of the logits, and the push 2 a - 1 the env takes (exactly +-1 for the two actions).
+        // Every lane of every wave is here (the row step shuffles); lane 0 is the slot's only reader.
+        const CatRow c = categorical_row<LPE>(L.t.mu + r * A, A, l, L.kes[r], !det);
+        if (l == 0) L.actb[r] = 2.f * (float)c.a - 1.f;
+      } else {
+        if (a.kind == 0) {
+          for (int j = l; j < na; j += LPE) err += syn_err_term(act[r * A + j], L.st[r * S + j]);
+        }
 #pragma unroll
-      for (int o = LPE / 2; o > 0; o >>= 1) err += __shfl_xor(err, o, LPE);
+        for (int o = LPE / 2; o > 0; o >>= 1) err += __shfl_xor(err, o, LPE);
+      }
       if (l == 0) {
         bool term;
-        const float rew = env_reward(a.kind, L.st, S, act, A, r, err, na, a.key_term, (uint32_t)(e0 + r), kstep, term);
+        const float rew = env_reward(kind, L.st, S, act, actA, r, err, na, a.key_term, (uint32_t)(e0 + r), kstep, term);
         const int el = L.envlen[r] + 1;
         const bool done = term || (el >= a.limit);
         L.envlen[r] = done ? 0 : el;
@@ -141,7 +154,7 @@ __global__ __launch_bounds__(NW * 64) void eval_kernel(EvalArgs a) {
     }
     __syncthreads();
     // ---- (e) state transition (+ in-place reset on done) ----
-    env_transition<ROWS, NTHR>(a.kind, L.st, S, act, A, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
+    env_transition<ROWS, NTHR>(kind, L.st, S, act, actA, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
     __syncthreads();
     // every valid env of the tile has finished: read after the step's closing barrier (nfin's next
     // writer is the next step's phase (d), barriers away), so the exit is workgroup-uniform
@@ -160,6 +173,18 @@ extern "C" void launch_eval(int dt, const EvalArgs& a, hipStream_t s) {
   dispatch_dt(dt, [&](auto d) {
     constexpr int DT = decltype(d)::value, ROWS = 16, NW = POLICY_WAVES<DT, ROWS>;
     const size_t lds = EvalLds<DT, ROWS>(nullptr, a).cv.off;
+    if (a.dist != 0) {   // the categorical forms: the cart-pole, not fp8 (the binding refuses the rest first)
+      if constexpr (DT != DT_FP8) {
+        if (a.kind == KIND_CARTPOLE) {
+          if (lds > 65536) set_max_lds_once<eval_kernel<DT, ROWS, NW, true>>(lds);
+          hipLaunchKernelGGL((eval_kernel<DT, ROWS, NW, true>), dim3((a.E + ROWS - 1) / ROWS), dim3(NW * 64), lds, s, a);
+          HIP_CHECK_LAUNCH();
+          return;
+        }
+      }
+      dppo_note_error(hipErrorInvalidValue, __FILE__, __LINE__);
+      return;
+    }
     if (lds > 65536) set_max_lds_once<eval_kernel<DT, ROWS, NW>>(lds);
     hipLaunchKernelGGL((eval_kernel<DT, ROWS, NW>), dim3((a.E + ROWS - 1) / ROWS), dim3(NW * 64), lds, s, a);
     HIP_CHECK_LAUNCH();

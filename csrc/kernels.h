@@ -75,6 +75,12 @@ struct RolloutArgs {
   float* trunc;        // [T][E] 0.f / 1.f, like dones
   void* x_fin;         // [fin_K][E][d1] storage precision (allocated zeroed by the host)
   int fin_K;           // >= ceil((t_base + T) / limit)
+  // (last: every earlier member keeps its kernel-argument offset)
+  // The policy head, as ActArgs::dist.  0: Gaussian.  1: categorical over A actions (policy_step.h categorical_row):
+  // the Gumbel-max sample keyed (key_action, env, step, k), `actions` gets ONE-HOT rows, logp the log-softmax of the
+  // chosen logit.  Cart-pole physics (kind 2) only, which is pushed +1 for index 1 and -1 for index 0; 16-row tiles,
+  // not fp8, not the per-step filter (sn_g1 null).
+  int dist;
 };
 
 // The per-step filter's partial-moment granules (RolloutArgs::sn_g1), line-blocked: a 128-byte
@@ -103,6 +109,8 @@ struct EvalArgs {
   // outputs, frozen at an env's first done
   float* ret;          // [E] sum of the unclipped rewards, added in step order
   int* len;            // [E] steps
+  // (last) the policy head as RolloutArgs::dist; 1 with deterministic: the arg-max of the logits
+  int dist;
 };
 
 // One policy step for caller-supplied observations (csrc/act.hip): E rows of raw fp32 observations

@@ -202,7 +202,10 @@ struct RolloutLds {
 // FIN: bootstrap_time_limit (RolloutArgs trunc / x_fin): step (d) marks the rows that ended by the
 // step limit alone, step (e) takes a cold branch for a tile that has one.  A template parameter so
 // that the forms without it keep their instructions and registers; never together with SN.
-template <int DT, int ROWS, int NW, bool SN, bool FIN>
+// CAT: the categorical head (RolloutArgs::dist 1) on the cart-pole's physics — phases (c) and (d) are one
+// per-env phase (policy_step.h categorical_row), one barrier per step fewer.  A template parameter for FIN's
+// reason, and the env kind is then a constant: the forms with it hold no other env's code.  Never with SN.
+template <int DT, int ROWS, int NW, bool SN, bool FIN, bool CAT = false>
 __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
   using P = Prec<DT>;
   using T = typename P::T;
@@ -210,10 +213,12 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
   static_assert(ROWS % 4 == 0 && NTHR % ROWS == 0 && (NTHR / ROWS) <= 64, "rollout tiling");
   static_assert(!SN || NW >= 4, "the per-step filter's reduce polls with waves 0-3");
   static_assert(!(SN && FIN), "the final rows are normalised with the launch's fixed statistics");
+  static_assert(!(SN && CAT), "the categorical head is not built into the per-step filter's forms");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int e0 = blockIdx.x * ROWS;
   const int nvalid = min(ROWS, a.E - e0);
   const int O = a.O, A = a.A, S = a.S, d1 = a.net.d1;
+  const int kind = CAT ? KIND_CARTPOLE : a.kind;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const RolloutLds<DT, ROWS, SN> L(smem, a);
@@ -394,7 +399,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
         }
       }
     }
-    env_kind_switch(a.kind, observe);
+    env_kind_switch(kind, observe);
     if (!last) ps.prefetch(wave, lane);
     __syncthreads();
     if constexpr (XO_FROM_LDS)
@@ -409,14 +414,16 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
     // ---- (b) policy MLP: PH(1..3) = fc1, fc2, fc3 (each incl. barrier) ----
     ps.layers(wave, lane, [&](auto l) { PH(decltype(l)::value); });
     // ---- (c) sample a = mu + sigma * eps ----
-    sample_loop<ROWS, NTHR>(L.kes, A, tid, true, [&](int r, int j, float eps) {
-      const float av = L.t.mu[r * A + j] + L.lsg[A + j] * eps;
-      L.act[r * A + j] = av;
-      L.epsb[r * A + j] = eps;
-      if (r < nvalid) a.actions[((size_t)tb * a.buf_E + e0 + r) * A + j] = av;
-    });
-    __syncthreads();
-    PH(4);   // (c) sample
+    if constexpr (!CAT) {
+      sample_loop<ROWS, NTHR>(L.kes, A, tid, true, [&](int r, int j, float eps) {
+        const float av = L.t.mu[r * A + j] + L.lsg[A + j] * eps;
+        L.act[r * A + j] = av;
+        L.epsb[r * A + j] = eps;
+        if (r < nvalid) a.actions[((size_t)tb * a.buf_E + e0 + r) * A + j] = av;
+      });
+      __syncthreads();
+      PH(4);   // (c) sample
+    }
     // ---- (d) per-env: logp, reward, termination, episode bookkeeping ----
     // LPE lanes per env (contiguous inside a wave) share the per-dim sums, then reduce by shuffles
     {
@@ -425,19 +432,34 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
       const int e = e0 + r;
       float lp = 0.f, err = 0.f;
       const int na = min(A, O);
-      for (int j = l; j < A; j += LPE) {
-        lp += logp_term(L.epsb[r * A + j], L.lsg[j]);
-        if (a.kind == 0 && j < na) err += syn_err_term(L.act[r * A + j], L.st[r * S + j]);
-      }
+      if constexpr (CAT) {
+        // (c') + (d): mu holds the row's A logits, published by fc3's barrier like the key prefixes — no sample
+        // loop, no noise tile, no barrier of its own.  Every lane of every wave is here (the row step shuffles).
+        const CatRow c = categorical_row<LPE>(L.t.mu + r * A, A, l, L.kes[r], true);
+        if (r < nvalid) {
+          float* arow = a.actions + ((size_t)tb * a.buf_E + e) * A;
+          for (int k = l; k < A; k += LPE) arow[k] = (k == c.a) ? 1.f : 0.f;   // the one-hot row
+        }
+        lp = c.logp;
+        // the push CartPoleEnv._dynamics feeds its parent: 2 a - 1, exactly +-1 for the two actions.  This lane
+        // is the slot's only reader (env_reward below; the cart-pole's transition reads no action).
+        if (l == 0) L.act[r] = 2.f * (float)c.a - 1.f;
+      } else {
+        for (int j = l; j < A; j += LPE) {
+          lp += logp_term(L.epsb[r * A + j], L.lsg[j]);
+          if (a.kind == 0 && j < na) err += syn_err_term(L.act[r * A + j], L.st[r * S + j]);
+        }
 #pragma unroll
-      for (int o = LPE / 2; o > 0; o >>= 1) {
-        lp += __shfl_xor(lp, o, LPE);
-        err += __shfl_xor(err, o, LPE);
+        for (int o = LPE / 2; o > 0; o >>= 1) {
+          lp += __shfl_xor(lp, o, LPE);
+          err += __shfl_xor(err, o, LPE);
+        }
       }
       if (l == 0) {
-        lp -= logp_const(A);
+        if constexpr (!CAT) lp -= logp_const(A);
         bool term;
-        const float rew = env_reward(a.kind, L.st, S, L.act, A, r, err, na, a.key_term, (uint32_t)e, kstep, term);
+        // (CAT: the push row [ROWS][1])
+        const float rew = env_reward(kind, L.st, S, L.act, CAT ? 1 : A, r, err, na, a.key_term, (uint32_t)e, kstep, term);
         int el = L.eplen[r] + 1;
         float er_ = L.epret[r] + rew;
         bool done = term || (el >= a.limit);
@@ -480,7 +502,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
       if (tid < ROWS && L.done_s[tid] > 1.5f) L.done_s[tid] = -1.f;
       __syncthreads();
     }
-    env_transition<ROWS, NTHR>(a.kind, L.st, S, L.act, A, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
+    env_transition<ROWS, NTHR>(kind, L.st, S, L.act, A, L.done_s, L.kes, L.wdrv, L.jdx, a.key_reset, e0, kstep, tid);
     if (anyt) {
       __syncthreads();
       // the rows as step (a) makes them, through the input tile (free until the next observe):
@@ -496,7 +518,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
           }
         }
       };
-      env_kind_switch(a.kind, final_rows);
+      env_kind_switch(kind, final_rows);
       __syncthreads();
       const int slot = tb / a.limit;
       if (slot < a.fin_K) {
@@ -512,7 +534,7 @@ __global__ __launch_bounds__(NW * 64) void rollout_kernel(RolloutArgs a) {
           }
         }
       }
-      env_reset_rows<ROWS, NTHR>(a.kind, L.st, S, L.done_s, L.kes, a.key_reset, e0, kstep, tid);
+      env_reset_rows<ROWS, NTHR>(kind, L.st, S, L.done_s, L.kes, a.key_reset, e0, kstep, tid);
     }
     __syncthreads();
     PH(6);   // (e) env transition
@@ -617,6 +639,31 @@ void launch(const RolloutArgs& a, hipStream_t s) {
   if (e != hipSuccess) dppo_note_error(e, __FILE__, __LINE__);
 }
 
+// RolloutArgs::dist 1: the categorical forms exist for 16-row tiles at fp32 / bf16x3 / bf16, in the
+// precision's default wave count (set_rollout_waves is the Gaussian forms' A/B switch), with FIN on
+// and off; anything else is the binding's to refuse, and an error here
+void launch_categorical(int dt, const RolloutArgs& a, int rows, hipStream_t s) {
+  if (rows != 16 || dt == DT_FP8 || a.sn_g1 != nullptr || a.kind != KIND_CARTPOLE) {
+    dppo_note_error(hipErrorInvalidValue, __FILE__, __LINE__);
+    return;
+  }
+  dispatch_dt(dt, [&](auto d) {
+    constexpr int DT = decltype(d)::value, ROWS = 16, NW = POLICY_WAVES<DT, ROWS>;
+    if constexpr (DT != DT_FP8) {
+      const int nblk = (a.E + ROWS - 1) / ROWS;
+      const size_t lds = RolloutLds<DT, ROWS, false>(nullptr, a).cv.off;
+      auto go = [&](auto fin) {
+        constexpr bool FIN = decltype(fin)::value;
+        if (lds > 65536) set_max_lds_once<rollout_kernel<DT, ROWS, NW, false, FIN, true>>(lds);
+        hipLaunchKernelGGL((rollout_kernel<DT, ROWS, NW, false, FIN, true>), dim3(nblk), dim3(NW * 64), lds, s, a);
+      };
+      if (a.x_fin != nullptr) go(std::true_type{});
+      else go(std::false_type{});
+      HIP_CHECK_LAUNCH();
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" void set_rollout_waves(int nw) { g_rollout_waves = nw; }
@@ -632,6 +679,7 @@ extern "C" int rollout_stepnorm_cap(int dt, const RolloutArgs& a, int rows) {
 }
 
 extern "C" void launch_rollout(int dt, const RolloutArgs& a, int rows, hipStream_t s) {
+  if (a.dist != 0) return launch_categorical(dt, a, rows, s);
   dispatch_form(dt, rows, [&](auto d, auto r, auto w) {
     launch<decltype(d)::value, decltype(r)::value, decltype(w)::value>(a, s);
   });

@@ -48,8 +48,9 @@ class Params:
                                          # kind, device-stepped otherwise) | gym (gym.make, host-stepped)
     env_fused: bool = False              # GPU engine: run an env that has an in-kernel twin (VecEnv.kernel_kind) inside the
                                          # rollout / evaluation kernels; changes nothing for the synthetic envs and the
-                                         # pendulum (always in-kernel), moves CartPoleContinuous-v1 off the device-stepped
-                                         # path; an env without a kernel kind is refused.  The CPU engine ignores it.
+                                         # pendulum (always in-kernel), moves CartPoleContinuous-v1 and the discrete
+                                         # CartPole-v0 (the kernels' categorical head) off the device-stepped path; an env
+                                         # without a kernel kind (CartPole-v1 among them) is refused.  The CPU engine ignores it.
     env_module: str = ""                 # dotted module path imported once at start (worker, evaluator process,
                                          # play.py) so that it can call envs.register_tensor_env; "" = none
     host_policy: str = "torch"           # env_backend gym on the GPU engine, the per-step policy: torch (fp32 tensor

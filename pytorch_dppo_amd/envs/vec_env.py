@@ -265,6 +265,18 @@ class CartPoleEnv(CartPoleContinuousEnv):
 register_tensor_env("CartPole-v1", CartPoleEnv, obs_dim=4, act_dim=2, time_limit=500, discrete=True)
 
 
+class CartPoleV0Env(CartPoleEnv):
+    """gym CartPole-v0: CartPole-v1 with a 200-step limit — the same class but for one attribute.  It owns the
+    in-kernel twin of the discrete cart-pole: kernel kind KIND_CARTPOLE (the parent's physics, csrc/env_core.h
+    ``cartpole_next``) under the categorical head (``dist`` 1 of the rollout / evaluation kernels: index 1 pushes
+    +1, index 0 pushes -1, this ``_dynamics``' own ``2 a - 1``), which ``env_fused`` selects.  Without the flag it
+    is device-stepped like ``CartPole-v1``, whose name stays unfused."""
+    kernel_kind = KIND_CARTPOLE
+
+
+register_tensor_env("CartPole-v0", CartPoleV0Env, obs_dim=4, act_dim=2, time_limit=200, discrete=True)
+
+
 def make_vec_env(spec: EnvSpec, num_envs: int, seed: int = 1, rank: int = 0, device="cpu",
                  max_episode_length: int = 10000, backend: str = "builtin", name: str = ""):
     """``builtin``: the tensor envs above and the registered ones (``register_tensor_env``) — stepped

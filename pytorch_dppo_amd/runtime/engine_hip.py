@@ -409,9 +409,14 @@ class HipEngine(Engine):
         elif bool(getattr(params, "env_fused", False)):
             self.kernel_kind = kernel_kind_of(env)
         self.stepped_env = not self.host_env and self.kernel_kind is None
-        if self.discrete and not self.stepped_env:
-            raise ValueError(f"env {env.spec.name!r} has discrete actions: the rollout and evaluation kernels have the "
-                             "Gaussian head, a discrete env runs device-stepped (not with env_fused)")
+        # a discrete env whose class has a kernel kind (CartPole-v0): the fused kernels run it with the categorical
+        # head (RolloutArgs / EvalArgs dist 1, docs/ARCHITECTURE.md §29); their check_env refuses what has no such form
+        self.kernel_dist = 1 if self.discrete and not self.stepped_env else 0
+        if self.kernel_dist and params.obs_norm_update == "step":
+            raise ValueError(f"env {env.spec.name!r} with env_fused and obs_norm_update=step: the categorical head is "
+                             "not built into the per-step observation filter's launch forms (the register-tight "
+                             "4-wave forms of the rollout kernel); use obs_norm_update=rollout, or run it "
+                             "device-stepped (without env_fused)")
         # bootstrap_time_limit: which steps ended by the step limit alone (trunc, like dones), the
         # normalised observation each reached before its reset (x_fin [K][E][d0] in x_buf's storage:
         # slot t // limit, an env's truncations being >= limit steps apart) and its value.  Transient:
@@ -855,12 +860,13 @@ class HipEngine(Engine):
         rollout_fin take (*head, mean_f32, inv_std_f32, *tail, xT, xT rows[, trunc, x_fin, fin_K]),
         ext.rollout_stepnorm (*head, *tail, its stats and granule buffers).
         ints = [env kind, E, O, A, state dim, steps T of this launch, its first buffer step t_base, the
-        buffer's envs per step (E), step key t0 of its first step (32 bits), episode step limit, std_var];
+        buffer's envs per step (E), step key t0 of its first step (32 bits), episode step limit, std_var,
+        the policy head (0 Gaussian, 1 categorical)];
         keys = [env, terminal, reset, action]."""
         e = self.env
         kp = e.kernel_params()
         ints = [self._kind(), self.E, self.O, self.A, e.state_dim, T, t_base, self.E, t0 & 0xFFFFFFFF,
-                kp["limit"], self.std_var]
+                kp["limit"], self.std_var, self.kernel_dist]
         keys = [kp["key_env"], kp["key_term"], kp["key_reset"], self.key_action]
         return ((self.dt_fwd, ROLL_ROWS, e.state, e.ep_len, e.ep_ret, self.wimg_fwd, self.layout, self.scales,
                  self.model.flat.data),
@@ -1258,7 +1264,8 @@ class HipEngine(Engine):
         e = self.env
         k = eval_keys(self.p.seed)
         limit = int(min(e.spec.time_limit, self.p.max_episode_length))
-        ints = [self._kind(), E, self.O, self.A, e.state_dim, limit, self.std_var, 1 if deterministic else 0]
+        ints = [self._kind(), E, self.O, self.A, e.state_dim, limit, self.std_var, 1 if deterministic else 0,
+                self.kernel_dist]
         keys = [k["key_env"], k["key_term"], k["key_reset"], k["key_action"]]
         self.ext.eval_rollout(self.dt_fwd, self.wimg_fwd, self.layout, self.scales, self.model.flat.data,
                               self.stats.mean_f32, self.stats.inv_std_f32, ret, length, ints, keys, self.qscale)
